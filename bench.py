@@ -7,10 +7,23 @@ per ray.  One step = Trainer.train_step: ray sampling (randperm on device), ray
 generation, fused HIP render forward, rgb-L2 + depth-L1 loss, fused HIP backward,
 gradient all-reduce over RCCL (N > 1), Adam.  Inputs are resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (N > 1)
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (the field-MLP GEMM family,
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, W warm-up
+steps, the K timed steps (on one GPU as replays of the captured step, see --exec below; N > 1
+eager), the result line ("value", "ms_per_step" = milliseconds per timed step).  Everything
+else below -- the second execution mode, "roofline", "cpu_baseline", "alt_gemm", "render_cfg4",
+"full_cfg3", the per-step medians -- takes passes of its own and is measured only with --full;
+a plain run prints those keys as null.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, as float32
+DIR/<name>.npy: every tensor of the loss dict Trainer.train_step returned (loss.npy,
+l2_mean.npy, ...) and the field's parameters after that step's Adam update (param.<state_dict
+key>.npy; ~2.4 MB in all).  Scene, initial weights, ray draws and stratified noise are seeded,
+so two runs with the same arguments train on identical inputs.
+
+--full extra objects: "roofline" (the field-MLP GEMM family,
 timed live with hipEvents around every GEMM launch of the timed steps), "cpu_baseline"
 (the oracle CPU restatement of the same step on this host's cores, bounded sample) and
 "alt_gemm" (the same workload with the other GEMM arithmetics).  The GEMMs compute f32
@@ -20,10 +33,13 @@ accumulated in f32 (bf16x6), or as a row-scaled 2-word fp16 split with three pro
 (DESIGN.md section 4, tests/test_gpu_kernels.py::test_split_accuracy); the exact-f32
 number of the same run is "value_exact_f32".
 
-Execution (--exec, default auto): on one GPU the K steps are timed twice -- enqueued eagerly
-from Python, and as one captured hipGraph of the whole step replayed K times (new rays every
-replay from the sampler's device step counter) -- and "value" is the faster; "execution",
-"ms_per_step_eager" and "ms_per_step_graph" say which and give both.  Both are the full step
+Execution (--exec, default auto): on one GPU the K steps run as one captured hipGraph of the
+whole step replayed K times (new rays every replay from the sampler's device step counter), or
+enqueued eagerly from Python.  A plain auto run times the replays (the same GPU work without
+the host's enqueue time; on a fast host core the two are within 1 %, BENCH_r06.json) and falls
+back to eager only if capture fails; with --full the K steps are timed both ways and "value"
+is the faster.  "execution", "ms_per_step_eager" and "ms_per_step_graph" say which ran and give
+what was timed.  Both are the full step
 (nothing is cached or skipped); the graph only removes the host's ~1.9 ms (fast core) to
 > 3 ms (slow core) of Python enqueue per step from the timed region, which on a slow host
 is longer than the GPU's step.  N > 1 runs eager.
@@ -473,18 +489,25 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: both execution modes, the GEMM roofline "
+                         "(a second, instrumented pass), the other GEMM arithmetics, the config-4 render line, "
+                         "the config-3 line and the CPU baseline (each can be switched off with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss dict tensors, field parameters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--gemm-precision", choices=list(PRECISION), default=DEFAULT_GEMM,
                     help="GEMM arithmetic: f32 emulated by a row-scaled 2-word fp16 split (f16x3, default), by a "
                          "3-word bf16 split (bf16x6), or the exact-f32 MFMA (f32); all f32-accurate")
     ap.add_argument("--exec", dest="exec_mode", choices=["auto", "eager", "graph"], default="auto",
-                    help="auto (1 GPU): time the step eager AND as one replayed hipGraph, report the faster; "
-                         "N > 1 runs eager (RCCL capture is not exercised on this pool)")
+                    help="auto (1 GPU): time the step as one replayed hipGraph (eager if capture fails); with --full "
+                         "time it eager AND replayed, report the faster; N > 1 runs eager (RCCL capture is not "
+                         "exercised)")
     ap.add_argument("--no-alt", dest="alt", action="store_false",
-                    help="skip timing the other GEMM arithmetics (reported as alt_gemm)")
+                    help="--full: skip timing the other GEMM arithmetics (reported as alt_gemm)")
     ap.add_argument("--no-cfg3", dest="cfg3", action="store_false",
-                    help="skip the config-3 line (full NoPe-NeRF step, eager and graph; 1 GPU)")
+                    help="--full: skip the config-3 line (full NoPe-NeRF step, eager and graph; 1 GPU)")
     ap.add_argument("--cfg3-steps", type=int, default=20)
     ap.add_argument("--plumbing", action="store_true",
                     help="CPU gloo check of the rank launcher + gradient all-reduce (tests), no GPU")
@@ -506,6 +529,19 @@ def main():
     data, c2w = synthetic_scene(dev)
     medians = {}      # median per-step milliseconds (hipEvents at the step boundaries) per timed pass
     attributions = {}  # N > 1: per-rank all-reduce / compute split of the timed pass (rank_attribution)
+    snaps = {}        # --dump-outputs: host copies of the last timed step's outputs, per execution mode
+    main_prec = PRECISION[args.gemm_precision]
+
+    def snapshot(mode, net, ld):
+        """Host float32 copies of what the last timed step of the headline pass left: the loss dict
+        train_step returned and the field's parameters after its Adam update."""
+        if not args.dump_outputs or rank != 0:
+            return
+        torch.cuda.synchronize()
+        arrs = {k: v.detach().to("cpu", torch.float32).numpy().copy() for k, v in ld.items() if torch.is_tensor(v)}
+        for k, v in net.state_dict().items():
+            arrs["param." + k] = v.detach().to("cpu", torch.float32).numpy().copy()
+        snaps[mode] = arrs
 
     def measure(precision, with_hooks=True):
         """W warm-up + K timed train steps with the GEMMs in `precision` (0 exact-f32 MFMA,
@@ -557,6 +593,8 @@ def main():
             one(i)
         timed.attribution = None
         el, ld, _, _ = timed(args.warmup, False)
+        if precision == main_prec:
+            snapshot("eager", net, ld)
         medians[precision] = timed.median_ms
         attributions[precision] = timed.attribution
         if with_hooks:
@@ -572,7 +610,7 @@ def main():
         host enqueue (~1.9 ms on a fast host core, > 3 ms on a slow one) drops out of the timed
         region.  Returns (seconds for K replays, loss dict) or None if capture is not possible."""
         _hip.gemm_set_precision(precision)
-        trainer, _ = build_trainer(dev, c2w, cfg)
+        trainer, net = build_trainer(dev, c2w, cfg)
         trainer.enable_graph_rng()
         step = lambda i: trainer.train_step(data, it=i, epoch=0, scheduling_start=0)  # noqa: E731
         try:
@@ -594,12 +632,17 @@ def main():
         torch.cuda.synchronize()
         # the timed K replays carry no per-replay events (an event behind every replay cost
         # ~0.02 ms per step: profiles/r06/graph_timing_probe.json); the per-replay median comes
-        # from a second, untimed pass
+        # from a second, untimed pass (--full only)
         t0 = time.perf_counter()
         for i in range(args.steps):
             g.replay()
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
+        snapshot("graph", net, out)
+        if not args.full:
+            if not math.isfinite(out["loss"].detach().item()):
+                raise RuntimeError("graph replay: non-finite loss")
+            return el, out
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         evs[0].record()
         for i in range(args.steps):
@@ -611,19 +654,30 @@ def main():
             raise RuntimeError("graph replay: non-finite loss")
         return el, out
 
-    main_prec = PRECISION[args.gemm_precision]
-    elapsed, ld, (gemm_ms, gemm_launches, _, gemm_union_ms), kinds, net, elapsed_hooks = measure(main_prec)
-    elapsed_eager = elapsed
-    graph = None
-    if world == 1 and args.exec_mode in ("auto", "graph"):
+    want_graph = world == 1 and args.exec_mode in ("auto", "graph")
+    graph = hook_stats = kinds = net = elapsed_hooks = elapsed_eager = None
+    if not args.full and want_graph:
+        # plain run: the K steps are timed once, as replays; eager only if capture fails
+        graph = measure_graph(main_prec)
+        if graph is not None:
+            elapsed, ld = graph
+    if args.full or graph is None:
+        elapsed, ld, hook_stats, kinds, net, elapsed_hooks = measure(main_prec, with_hooks=args.full)
+        elapsed_eager = elapsed
+    if args.full and want_graph:
         graph = measure_graph(main_prec)
         if graph is not None and (args.exec_mode == "graph" or graph[0] < elapsed):
             elapsed, ld = graph
     execution = "graph replay" if (graph is not None and elapsed == graph[0]) else "eager"
     if args.exec_mode == "graph" and execution != "graph replay":
         raise RuntimeError("--exec graph: capture failed")
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in snaps["graph" if execution == "graph replay" else "eager"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     alt = None
-    if args.alt:
+    if args.full and args.alt:
         # the other GEMM arithmetics on the same workload, reported beside the headline
         alt = []
         for name, prec in PRECISION.items():
@@ -640,94 +694,101 @@ def main():
 
     if rank == 0:
         ms = 1e3 * elapsed / args.steps
-        # per-kind rooflines (MFMA and HBM ceilings, per-launch averages of the live records)
-        per_kind = {}
-        for k, rec in kinds.items():
-            r = kind_roofline(rec)
-            if r is not None:
-                r["launches_per_step"] = rec["launches"] / args.steps
-                r["ms_per_step"] = rec["ms"] / args.steps
-                r["what"] = KIND_NAMES[k]
-                r["kernel"] = KERNEL[args.gemm_precision][k]
-                per_kind[k] = r
-        dom = max(per_kind, key=lambda k: per_kind[k]["ms_per_step"])
-        d = per_kind[dom]
-        bound = d["binding"]
-        ach, peak, unit = ((d["hbm"]["achieved_gbs"], HBM_PEAK_GBS, "GB/s") if bound == "hbm" else
-                           (d["mfma"]["achieved_tflops_f32eq"], d["mfma"]["peak_tflops_f32eq"], "TFLOP/s"))
-        tpath = next((q for q in (os.path.join(ROOT, "profiles", r, "gemm_traffic.json")
-                                  for r in ("r06", "r05", "r04")) if os.path.exists(q)), "")
-        tkinds = json.load(open(tpath)).get("kinds", {}) if tpath and args.gemm_precision == "f16x3" else {}
 
-        def kind_traffic(k):
-            # HBM bytes per launch of kind k from the committed rocprofv3 PMC passes (FETCH_SIZE x2 +
-            # WRITE_SIZE, the guide's gfx950 correction): the mean over the kind's launches, as
-            # per_kind's algorithmic bytes are
-            kd = tkinds.get(k)
-            if not kd:
-                return None, None
-            return kd["bytes_per_launch"], (
-                f"{os.path.relpath(tpath, ROOT)}: mean over {kd['launches_profiled']} profiled launches of the "
-                f"kind's kernels ({kd['read_bytes_per_launch'] / 1e6:.1f} MB read, "
-                f"{kd['write_bytes_per_launch'] / 1e6:.1f} MB written per launch)")
+        def gemm_roofline():
+            """--full: the "roofline" object from the instrumented pass's per-kind records."""
+            gemm_ms, gemm_launches, _, gemm_union_ms = hook_stats
+            # per-kind rooflines (MFMA and HBM ceilings, per-launch averages of the live records)
+            per_kind = {}
+            for k, rec in kinds.items():
+                r = kind_roofline(rec)
+                if r is not None:
+                    r["launches_per_step"] = rec["launches"] / args.steps
+                    r["ms_per_step"] = rec["ms"] / args.steps
+                    r["what"] = KIND_NAMES[k]
+                    r["kernel"] = KERNEL[args.gemm_precision][k]
+                    per_kind[k] = r
+            dom = max(per_kind, key=lambda k: per_kind[k]["ms_per_step"])
+            d = per_kind[dom]
+            bound = d["binding"]
+            ach, peak, unit = ((d["hbm"]["achieved_gbs"], HBM_PEAK_GBS, "GB/s") if bound == "hbm" else
+                               (d["mfma"]["achieved_tflops_f32eq"], d["mfma"]["peak_tflops_f32eq"], "TFLOP/s"))
+            tpath = next((q for q in (os.path.join(ROOT, "profiles", r, "gemm_traffic.json")
+                                      for r in ("r06", "r05", "r04")) if os.path.exists(q)), "")
+            tkinds = json.load(open(tpath)).get("kinds", {}) if tpath and args.gemm_precision == "f16x3" else {}
 
-        traffic, traffic_note = kind_traffic(dom)
-        # the longest single in-step kernel (the training forward chain since round 4), priced
-        # against its own binding ceiling: comparable across rounds whichever kind has the most
-        # time per step
-        dk = max(per_kind, key=lambda k: per_kind[k]["avg_launch_us"])
-        dkr = per_kind[dk]
-        dk_hbm = dkr["binding"] == "hbm"
-        dk_traffic, dk_note = kind_traffic(dk)
-        dominant = {"kind": dk, "kernel": dkr["kernel"], "bound": dkr["binding"],
-                    "avg_launch_us": dkr["avg_launch_us"],
-                    "achieved": dkr["hbm"]["achieved_gbs"] if dk_hbm else dkr["mfma"]["achieved_tflops_f32eq"],
-                    "peak": HBM_PEAK_GBS if dk_hbm else dkr["mfma"]["peak_tflops_f32eq"],
-                    "unit": "GB/s" if dk_hbm else "TFLOP/s",
-                    "frac": dkr["hbm"]["frac"] if dk_hbm else dkr["mfma"]["frac"],
-                    "algorithmic_mbytes_per_launch": dkr["mbytes_per_launch"],
-                    "gflop_per_launch": dkr["gflop_per_launch"],
-                    "traffic": dk_traffic, "traffic_note": dk_note}
-        nt_fl, tn_fl = algorithmic_gemm_flops(net, RAYS * SAMPLES, split=True)
-        fam_ms = sum(rec["ms"] for rec in kinds.values())
-        fam_mfma = sum(rec["mfma_flops"] for rec in kinds.values())
-        roof = {"bound": bound, "kernel": d["kernel"], "what": d["what"],
-                "achieved": ach, "peak": peak, "unit": unit, "frac": ach / peak, "traffic": traffic,
-                "flop_basis": ("f32-equivalent: algorithmic f32 products; the fp16-pair kernels issue 3 fp16 MFMA "
-                               "products per f32 product, so the peak is the dense fp16 MFMA peak / 3"
-                               if bound == "mfma" else None),
-                "traffic_note": traffic_note,
-                "other_ceiling": ({"mfma_frac": d["mfma"]["frac"], "mfma_achieved_tflops_f32eq":
-                                   d["mfma"]["achieved_tflops_f32eq"], "mfma_peak_tflops_f32eq":
-                                   d["mfma"]["peak_tflops_f32eq"]} if bound == "hbm" else
-                                  {"hbm_frac": d["hbm"]["frac"], "hbm_achieved_gbs": d["hbm"]["achieved_gbs"]}),
-                "dominant_kernel": dominant,
-                "per_kind": per_kind,
-                "family": {"gemm_ms_per_step": gemm_ms / args.steps, "union_ms_per_step": gemm_union_ms / args.steps,
-                           "launches_per_step": gemm_launches / args.steps,
-                           "algorithmic_gflop_per_step": (nt_fl + tn_fl) / 1e9,
-                           "mfma_frac_per_launch": (fam_mfma / (BF16_MFMA_PEAK_TFLOPS * 1e12 if
-                                                                args.gemm_precision != "f32" else
-                                                                FP32_MFMA_PEAK_TFLOPS * 1e12)) / (fam_ms * 1e-3)},
-                "timing": "per-kind hipEvent pairs around every GEMM launch on its own stream, second timed "
-                          "pass of the same K steps (ms_per_step of that pass: %.3f)" % (1e3 * elapsed_hooks /
-                                                                                          args.steps)}
-        render = render_frame_line(dev) if world == 1 and args.gemm_precision == "f16x3" else None
+            def kind_traffic(k):
+                # HBM bytes per launch of kind k from the committed rocprofv3 PMC passes (FETCH_SIZE x2 +
+                # WRITE_SIZE, the gfx950 counter units): the mean over the kind's launches, as
+                # per_kind's algorithmic bytes are
+                kd = tkinds.get(k)
+                if not kd:
+                    return None, None
+                return kd["bytes_per_launch"], (
+                    f"{os.path.relpath(tpath, ROOT)}: mean over {kd['launches_profiled']} profiled launches of the "
+                    f"kind's kernels ({kd['read_bytes_per_launch'] / 1e6:.1f} MB read, "
+                    f"{kd['write_bytes_per_launch'] / 1e6:.1f} MB written per launch)")
+
+            traffic, traffic_note = kind_traffic(dom)
+            # the longest single in-step kernel (the training forward chain since round 4), priced
+            # against its own binding ceiling: comparable across rounds whichever kind has the most
+            # time per step
+            dk = max(per_kind, key=lambda k: per_kind[k]["avg_launch_us"])
+            dkr = per_kind[dk]
+            dk_hbm = dkr["binding"] == "hbm"
+            dk_traffic, dk_note = kind_traffic(dk)
+            dominant = {"kind": dk, "kernel": dkr["kernel"], "bound": dkr["binding"],
+                        "avg_launch_us": dkr["avg_launch_us"],
+                        "achieved": dkr["hbm"]["achieved_gbs"] if dk_hbm else dkr["mfma"]["achieved_tflops_f32eq"],
+                        "peak": HBM_PEAK_GBS if dk_hbm else dkr["mfma"]["peak_tflops_f32eq"],
+                        "unit": "GB/s" if dk_hbm else "TFLOP/s",
+                        "frac": dkr["hbm"]["frac"] if dk_hbm else dkr["mfma"]["frac"],
+                        "algorithmic_mbytes_per_launch": dkr["mbytes_per_launch"],
+                        "gflop_per_launch": dkr["gflop_per_launch"],
+                        "traffic": dk_traffic, "traffic_note": dk_note}
+            nt_fl, tn_fl = algorithmic_gemm_flops(net, RAYS * SAMPLES, split=True)
+            fam_ms = sum(rec["ms"] for rec in kinds.values())
+            fam_mfma = sum(rec["mfma_flops"] for rec in kinds.values())
+            return {"bound": bound, "kernel": d["kernel"], "what": d["what"],
+                    "achieved": ach, "peak": peak, "unit": unit, "frac": ach / peak, "traffic": traffic,
+                    "flop_basis": ("f32-equivalent: algorithmic f32 products; the fp16-pair kernels issue 3 fp16 "
+                                   "MFMA products per f32 product, so the peak is the dense fp16 MFMA peak / 3"
+                                   if bound == "mfma" else None),
+                    "traffic_note": traffic_note,
+                    "other_ceiling": ({"mfma_frac": d["mfma"]["frac"], "mfma_achieved_tflops_f32eq":
+                                       d["mfma"]["achieved_tflops_f32eq"], "mfma_peak_tflops_f32eq":
+                                       d["mfma"]["peak_tflops_f32eq"]} if bound == "hbm" else
+                                      {"hbm_frac": d["hbm"]["frac"], "hbm_achieved_gbs": d["hbm"]["achieved_gbs"]}),
+                    "dominant_kernel": dominant,
+                    "per_kind": per_kind,
+                    "family": {"gemm_ms_per_step": gemm_ms / args.steps,
+                               "union_ms_per_step": gemm_union_ms / args.steps,
+                               "launches_per_step": gemm_launches / args.steps,
+                               "algorithmic_gflop_per_step": (nt_fl + tn_fl) / 1e9,
+                               "mfma_frac_per_launch": (fam_mfma / (BF16_MFMA_PEAK_TFLOPS * 1e12 if
+                                                                    args.gemm_precision != "f32" else
+                                                                    FP32_MFMA_PEAK_TFLOPS * 1e12)) / (fam_ms * 1e-3)},
+                    "timing": "per-kind hipEvent pairs around every GEMM launch on its own stream, second timed "
+                              "pass of the same K steps (ms_per_step of that pass: %.3f)" % (1e3 * elapsed_hooks /
+                                                                                              args.steps)}
+
+        roof = gemm_roofline() if args.full else None
+        render = render_frame_line(dev) if args.full and world == 1 and args.gemm_precision == "f16x3" else None
         full = None
-        if world == 1 and args.cfg3:
+        if args.full and world == 1 and args.cfg3:
             log("timing config 3 (the full NoPe-NeRF step) ...")
             full = cfg3_line(dev, args.cfg3_steps, 3)
             _hip.gemm_set_precision(main_prec)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing the CPU baseline (oracle) ...")
             cpu = cpu_baseline(args.cpu_budget)
         exact = next((a for a in (alt or []) if a["gemm_arithmetic"] == "f32"), None)
         out = {"metric": METRIC, "value": world * RAYS / (elapsed / args.steps), "unit": "rays/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
-               "execution": execution,
-               "ms_per_step_median": medians["graph" if execution == "graph replay" else main_prec],
-               "ms_per_step_eager": 1e3 * elapsed_eager / args.steps,
+               "execution": execution, "full": args.full,
+               "ms_per_step_median": medians.get("graph" if execution == "graph replay" else main_prec),
+               "ms_per_step_eager": 1e3 * elapsed_eager / args.steps if elapsed_eager is not None else None,
                "ms_per_step_graph": 1e3 * graph[0] / args.steps if graph is not None else None,
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                "dtype": DTYPE[args.gemm_precision], "gemm_arithmetic": args.gemm_precision,

@@ -24,7 +24,7 @@ for step in "$@"; do
       timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || exit $?
       tail -1 $OUT/smoke.log ;;
     bench)
-      timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || exit $?
+      timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit $?
       python -c "import json;d=json.load(open('$OUT/bench.json'));print('bench', d['value'], d['ms_per_step'], d.get('ms_per_step_median'), d['execution'], d['roofline']['frac'], d.get('render_cfg4',{}).get('ms_per_frame'), d.get('full_cfg3',{}).get('ms_per_step'))" ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -o run -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt --exec eager > $OUT/prof_bench.log 2>&1) || exit $?

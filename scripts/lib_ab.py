@@ -36,7 +36,7 @@ def main():
             else:
                 env = dict(os.environ, NERF_HIP_LIB=os.path.join(ROOT, lib))
             out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps),
-                                  "--warmup", "5", "--no-alt", "--no-cpu-baseline", "--no-cfg3",
+                                  "--warmup", "5", "--full", "--no-alt", "--no-cpu-baseline", "--no-cfg3",
                                   "--exec", args.exec_mode], env=env, capture_output=True, text=True, timeout=600)
             line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
             if not line:
