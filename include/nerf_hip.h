@@ -242,6 +242,44 @@ typedef struct nerf_field_bwd {
 size_t nerf_field_bwd_workspace_bytes(int n_pad, int ray_grad);
 int nerf_field_backward(const nerf_field_bwd* args, void* stream, void* side_stream);
 
+/* The backward of a frozen field, down to the rays only (an addition within ABI 15): the
+ * autograd of rendering.py:113-141 and official_nerf.py:60-119 w.r.t. the sample points and view
+ * directions when no field parameter takes a gradient -- the pose-only step of
+ * eval_pose_one_epoch.py:30-76, where the reference computes the parameter gradients and never
+ * uses them.  Schedule, all on `stream` (no side stream): composite backward (or a given
+ * graw4), nerf_mlp_chain_bwd_rays, the three 64-wide nerf_linear_bwd_data launches over the
+ * encoding rows of W^T of the colour layer, l4 and l0, nerf_encode_bwd.  The launches and
+ * operands are those of nerf_field_backward with ray_grad = 1, bwd_chain = 1, so g_pts_o,
+ * g_pts_d and g_view are bit-identical to its.  It takes its own small struct: the forward
+ * state is what nerf_mlp_chain_frozen leaves (z, raw4, the ReLU words), never a layer output or
+ * a column maximum.  wt / wt_img are read for layers 0, 4 and 9 only, wt_cimg for 1..9.
+ * Hidden 256 / colour 128, GEMM precision mode 2.  The workspace holds graw4, three D_i with
+ * their row maxima and three encoding gradients (nerf_field_bwd_rays_workspace_bytes). */
+typedef struct nerf_field_bwd_rays {
+    int n_pad, n_rays, n_samples, flags;
+    const float* z;
+    const float* raw4;
+    const uint32_t* mask[NERF_BWD_LAYERS];  /* ReLU words [n_pad][out/32] (feature layer: NULL) */
+    const float* pts_o;                     /* ray inputs of nerf_encode_samples */
+    const float* pts_d;
+    const float* view;
+    const float* wt[NERF_BWD_LAYERS];       /* f32 W^T [kp][out_p] (layers 0, 4, 9) */
+    const uint16_t* wt_img[NERF_BWD_LAYERS];/* fp16 pair image of W^T (layers 0, 4, 9) */
+    const uint16_t* wt_cimg[NERF_BWD_LAYERS];/* its chain image (layers 1..9) */
+    const float* wd;                        /* fc_density weight [256], 16-byte aligned */
+    const float* wc;                        /* fc_rgb weight [3][128] */
+    /* upstream gradient: graw4 [n_pad][4], or g_rgb [R][3] + g_dist [R] through the composite */
+    const float* g_rgb;
+    const float* g_dist;
+    const float* graw4;
+    float* g_pts_o;                         /* [R][3] each */
+    float* g_pts_d;
+    float* g_view;
+    void* workspace;
+} nerf_field_bwd_rays;
+size_t nerf_field_bwd_rays_workspace_bytes(int n_pad);
+int nerf_field_backward_rays(const nerf_field_bwd_rays* args, void* stream);
+
 /* Recommended `splits` for nerf_linear_bwd_weight at this shape and tile policy. */
 int nerf_linear_bwd_weight_splits(int nout, int kin, int m);
 
@@ -322,6 +360,17 @@ int nerf_mlp_chain_fwd(const float* enc_p, const float* enc_d, const float* enc_
 int nerf_mlp_chain_train(const float* enc_p, const float* enc_d, const float* enc_p_rmax, const float* enc_d_rmax,
                          int n_pad, const nerf_chain_layer* layers, const float* wd, const float* bd, const float* wc,
                          const float* bc, float* raw4, void* stream);
+/* The frozen-field forward chain: nerf_mlp_chain_train for a render whose backward reaches only
+ * the rays (eval_pose_one_epoch.py:30-76 -- the pose-only step of evaluation/eval.py:117-141
+ * optimises optimizer_pose alone, the field of official_nerf.py:60-96 stays fixed).  The same
+ * kernel instantiated without its saves: the arithmetic, and so every ReLU word and raw4, is
+ * bit-identical to nerf_mlp_chain_train's, but no layer output and no column maximum is
+ * computed or stored.  Arguments as nerf_mlp_chain_train, except that `out` and `cmax` must be
+ * NULL for every layer (checked); `mask` stays mandatory (none for lf).  An addition within
+ * ABI 15: no existing entry point or struct changes. */
+int nerf_mlp_chain_frozen(const float* enc_p, const float* enc_d, const float* enc_p_rmax, const float* enc_d_rmax,
+                          int n_pad, const nerf_chain_layer* layers, const float* wd, const float* bd, const float* wc,
+                          const float* bc, float* raw4, void* stream);
 /* The fused per-ray eval render (BASELINE.json north_star; rendering.py:36-168 with eval_ /
  * no noise, official_nerf.py:60-119): ONE launch per ray chunk computes, per 128-row block
  * of S-sample rays (S divides 128), the stratified sample positions and both positional
@@ -373,6 +422,13 @@ typedef struct nerf_chain_bwd {
     int n_pad;
 } nerf_chain_bwd;
 int nerf_mlp_chain_bwd(const nerf_chain_bwd* a, void* stream);
+/* The ray-gradient chain: nerf_mlp_chain_bwd storing only what the ray gradients read
+ * (official_nerf.py:61-64, 87-90: the encodings enter l0, l4 and the colour layer) -- D_0, D_5
+ * (the gradient at l4's output), D_9 (at l0's) and their row maxima, bit-identical to
+ * nerf_mlp_chain_bwd's.  dy / lddy / dy_rmax are mandatory for i = 0, 5, 9; every other dy[i] and
+ * dy_rmax[i] and all of dy_cmax must be NULL (checked: they would stay unwritten); scratch is
+ * unused.  An addition within ABI 15. */
+int nerf_mlp_chain_bwd_rays(const nerf_chain_bwd* a, void* stream);
 
 /* Diagnostics only: per-block phase cycles of nerf_mlp_chain_fwd into buf[(n_pad/128)*6]
  * uint64 (DMA wait, barrier, MFMA section, epilogue, total, end time); NULL switches off. */
@@ -452,7 +508,7 @@ int nerf_encode_bwd(const float* pts_o, const float* pts_d, const float* view, c
  * 16 + 4 g + i - 4 (i >= 4) of the 32 (common.hpp chain_perm), the order in which the
  * 16x16x32 MFMA accumulators of the two-wave chains hold a layer's outputs.  perm_k % 32 == 0,
  * ld_t % 32 == 0 when dst_cts is given.  Since ABI 15 the chain images also hold every row's
- * exponent in a compact int32 array at plane 2's chunk 1 (u16 index ((2*K/8 + 1)*rows + 2 r)),
+ * exponent in a compact int32 array at plane 2's chunk 1 (u16 index (2*K/8 + 1)*rows*8 + 2 r),
  * which the chain kernels load with one 1 KB LDS-DMA per layer. */
 #define NERF_MAX_PACK 24
 typedef struct {

@@ -927,26 +927,30 @@ template <bool TR>
 constexpr int dma_in(int j) { return dma_step(j + npair<TR>() - 1); }
 // training, layer l >= 1, step u: the previous layer's output is saved two float4 stores per
 // tile pair (pairs 0 and 1 at u = 0, pair u + 1 at u = 1..6); at u = 0 of l >= 2 layer l - 2's
-// column maxima and ReLU words leave LDS (one store each).  All before the step's barrier
-template <bool TR>
+// column maxima and ReLU words leave LDS (one store each).  All before the step's barrier.
+// SV = false (the frozen-field forward, k_mlp_chain_frozen): no output and no column-maximum
+// stores exist, only layer l - 2's ReLU words -- the counts must drop with the stores (a
+// count above the ops issued would let a wait pass before its DMAs landed)
+template <bool TR, bool SV = TR>
 constexpr int pre_st(int k) {
     const int l = layer_of_k(k), u = k - kfirst(l);
     if (!TR || l == 0) return 0;
+    if (!SV) return u == 0 && l >= 2 ? 1 : 0;
     return u == 0 ? 4 + (l >= 2 ? 2 : 0) : (u <= 6 ? 2 : 0);
 }
 // the counted wait before B_{k+1} (at tile tb(k) of step k) for the DMAs of step k + 1, issued
 // behind B_{k + 3 - NPAIR} in step j0 = k + 2 - NPAIR (the prologue when negative): vmcnt counts
 // loads, stores and LDS-DMA together in issue order, so the count is every vector-memory op the
 // wave issued after them.  Ops left out of the count only make a wait stricter
-template <bool TR>
+template <bool TR, bool SV = TR>
 constexpr int wait_n(int k) {
     constexpr int P = npair<TR>();
     const int j0 = k + 2 - P;
     int n = 0;
     if (j0 < 0)
         for (int m = k + 2; m <= P - 2; ++m) n += dma_step(m);
-    for (int j = (j0 + 1 > 0 ? j0 + 1 : 0); j < k; ++j) n += pre_st<TR>(j) + dma_in<TR>(j);
-    return n + pre_st<TR>(k);
+    for (int j = (j0 + 1 > 0 ? j0 + 1 : 0); j < k; ++j) n += pre_st<TR, SV>(j) + dma_in<TR>(j);
+    return n + pre_st<TR, SV>(k);
 }
 // the prologue's wait for step 0 (it issues the DMAs of steps 0 .. NPAIR - 2)
 template <bool TR>
@@ -958,6 +962,8 @@ constexpr int wait_prologue() {
 static_assert(wait_n<true>(0) == dma_step(2) && wait_n<true>(1) == dma_in<true>(0), "training waits");
 static_assert(wait_n<true>(5) == pre_st<true>(4) + dma_in<true>(4) + pre_st<true>(5), "training waits");
 static_assert(wait_n<false>(0) == 0 && wait_n<false>(7) == 0, "eval waits");
+static_assert(wait_n<true, false>(0) == dma_step(2) && wait_n<true, false>(5) == dma_in<true>(4), "frozen waits");
+static_assert(wait_n<true, false>(10) == dma_in<true>(9) + 1, "frozen waits: l0's ReLU words leave at l2's first step");
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float pf2 __attribute__((ext_vector_type(2)));
@@ -1304,8 +1310,8 @@ static_assert(piece_tile<16>(P_STORE) <= 16 - 3 - 1 && piece_tile<16>(P0_STORE) 
                   piece_tile<8>(P_STORE_B) <= 8 - 2 - 1 && piece_tile<8>(P0_STORE_B) <= 8 - 2 - 1,
               "stores before the barrier");
 // training: the save work of layer l's k-step u (the previous layer's output, P = p.L[l - 1]),
-// piece j of ntj
-template <int l, int u, int j, int ntj>
+// piece j of ntj.  SV = false (frozen field): the ReLU words only -- no output store, no column maxima
+template <int l, int u, int j, int ntj, bool SV>
 __device__ __forceinline__ void save_pieces(const ChainFwdArgs& p, State& st) {
     using Y = LY<true>;
     if constexpr (l >= 1 && u < 8) {
@@ -1327,8 +1333,8 @@ __device__ __forceinline__ void save_pieces(const ChainFwdArgs& p, State& st) {
             return reinterpret_cast<uint32_t*>(st.lds + o) + par * 128 * MSKW + t;
         };
         const bool leader = (st.n & (16 / Q - 1)) == 0;
-        float* ob = P.out + st.m0 * 256;
-        constexpr bool CM = true, RW = relu, SV = true;
+        float* ob = SV ? P.out + st.m0 * 256 : nullptr;
+        constexpr bool CM = SV, RW = relu;
         if constexpr (u == 0) {
             if constexpr (SV && j == piece_tile<ntj>(P0_STORE)) tile_store4<256>(ob, st.vrow, 0, st.xs[0]);
             if constexpr (SV && j == piece_tile<ntj>(P0_STORE_B)) tile_store4<256>(ob, st.vrow, 64, st.xs[1]);
@@ -1406,7 +1412,7 @@ __device__ __forceinline__ void frag_reads(State& st) {
 // (its 128-row group) and its ReLU words, complete since layer l - 1's last step, leave LDS
 // -- wave w stores features 32 w .. + 31, lane (g, n) its row's words 2 g, 2 g + 1 -- and are
 // cleared for layer l's saves
-template <int l, bool TR>
+template <int l, bool TR, bool SV>
 __device__ __forceinline__ void layer_start(const ChainFwdArgs& p, State& st) {
     using Y = LY<TR>;
     const int tid = fresh(st.tid);
@@ -1415,12 +1421,14 @@ __device__ __forceinline__ void layer_start(const ChainFwdArgs& p, State& st) {
             1.f, -reinterpret_cast<const int*>(st.lds + Y::O_LEB + (l & 1) * 1024)[tid]);
     if constexpr (TR && l >= 2) {
         const int lane = tid & 63;
-        if (lane < 32) {
-            uint32_t* cm = reinterpret_cast<uint32_t*>(st.lds + Y::O_CMX);
-            const int cw = (l & 1) * 256 + 32 * st.wave + lane;
-            p.L[l - 2].cmax[(st.m0 / CROWS) * L_OUT[l - 2] + 32 * st.wave + lane] =
-                __uint_as_float(cm_read<CMQ_FWD>(cm, cw));
-            cm_clear<CMQ_FWD>(cm, cw);
+        if constexpr (SV) {
+            if (lane < 32) {
+                uint32_t* cm = reinterpret_cast<uint32_t*>(st.lds + Y::O_CMX);
+                const int cw = (l & 1) * 256 + 32 * st.wave + lane;
+                p.L[l - 2].cmax[(st.m0 / CROWS) * L_OUT[l - 2] + 32 * st.wave + lane] =
+                    __uint_as_float(cm_read<CMQ_FWD>(cm, cw));
+                cm_clear<CMQ_FWD>(cm, cw);
+            }
         }
         const int rl = 16 * st.wave + (lane & 15), g = lane >> 4;
         const nerf_chain_layer& Q = p.L[l - 2];
@@ -1433,7 +1441,7 @@ __device__ __forceinline__ void layer_start(const ChainFwdArgs& p, State& st) {
 // tile j of 32-k step u of layer l: the read of tile j + PF's fragments, this tile's three
 // MFMA products, the pieces placed behind it, and at tile tb the wait, barrier B_{k+1} and the
 // DMAs of step k + NPAIR - 1 (one 16-k step at tb, the other at tb + 1)
-template <int l, int u, bool TR, int j, int ntj>
+template <int l, int u, bool TR, bool SV, int j, int ntj>
 __device__ __forceinline__ void mstep_tiles(const ChainFwdArgs& p, State& st, const uint4& ah, const uint4& al) {
     constexpr int PF = pf_tiles<TR>(), R = PF + 1;
     constexpr int k = kfirst(l) + u, G = gtile(k) + j, T = tb<TR>(k);
@@ -1445,12 +1453,12 @@ __device__ __forceinline__ void mstep_tiles(const ChainFwdArgs& p, State& st, co
         st.acc[j] = mfma16(st.wh[G % R], al, st.acc[j]);   // hi . lo
         st.acc[j] = mfma16(st.wl[G % R], ah, st.acc[j]);   // lo . hi
         st.acc[j] = mfma16(st.wh[G % R], ah, st.acc[j]);   // hi . hi
-        if constexpr (u == 0 && j == 0) layer_start<l, TR>(p, st);
+        if constexpr (u == 0 && j == 0) layer_start<l, TR, SV>(p, st);
         split_pieces<l, u, j, ntj>(st);
-        if constexpr (TR) save_pieces<l, u, j, ntj>(p, st);
+        if constexpr (TR) save_pieces<l, u, j, ntj, SV>(p, st);
         if constexpr (k + 1 < NK && j == T) {
             tick(p, st, nullptr);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_n<TR>(k)) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_n<TR, SV>(k)) : "memory");
             tick(p, st, &st.t_wait);
             __syncthreads();
             tick(p, st, &st.t_bar);
@@ -1458,35 +1466,36 @@ __device__ __forceinline__ void mstep_tiles(const ChainFwdArgs& p, State& st, co
         }
         if constexpr (k + 1 < NK && j == T + DMA2) dma<tt_of_k(k + npair<TR>() - 1) + 1, TR>(p, st);
         __builtin_amdgcn_sched_barrier(0);
-        mstep_tiles<l, u, TR, j + 1, ntj>(p, st, ah, al);
+        mstep_tiles<l, u, TR, SV, j + 1, ntj>(p, st, ah, al);
     }
 }
 
 // one 32-k MFMA step u of layer l (16-k steps TT, TT + 1): 16 or 8 feature tiles x 3 products
 // over the fragments the ring already holds; the steps from the register tile split the next
 // step's A fragment and (training) save the previous layer's output beside the MFMAs
-template <int l, int u, bool TR>
+template <int l, int u, bool TR, bool SV>
 __device__ __forceinline__ void kstep(const ChainFwdArgs& p, State& st) {
     constexpr int nact = l == 0 ? 0 : 8;         // k-steps from the register tile, then the encoding
     constexpr int ntj = L_OUT[l] / 16;
     if constexpr (u == 0) frag_reads<gtile(kfirst(l)), pf_tiles<TR>(), TR>(st);   // published by B_k
     const uint4& ah = u < nact ? st.act_hi[u < nact ? u : 0] : st.enc_hi[u < nact ? 0 : u - nact];
     const uint4& al = u < nact ? st.act_lo[u < nact ? u : 0] : st.enc_lo[u < nact ? 0 : u - nact];
-    mstep_tiles<l, u, TR, 0, ntj>(p, st, ah, al);
+    mstep_tiles<l, u, TR, SV, 0, ntj>(p, st, ah, al);
 }
 
-template <int l, int u, bool TR>
+template <int l, int u, bool TR, bool SV>
 __device__ __forceinline__ void ksteps(const ChainFwdArgs& p, State& st) {
     if constexpr (2 * u < L_KS[l]) {
-        kstep<l, u, TR>(p, st);
-        ksteps<l, u + 1, TR>(p, st);
+        kstep<l, u, TR, SV>(p, st);
+        ksteps<l, u + 1, TR, SV>(p, st);
     }
 }
 
 // layer l: k-loop, epilogue (feature f = 16 j + 4 g + i of the lane's sample), heads, next A.
 // Training: the colour layer stores its f32 output and ReLU words here (no later layer
-// consumes it; every other layer's are saved by the next layer's k-steps)
-template <int l, bool TR>
+// consumes it; every other layer's are saved by the next layer's k-steps); the frozen-field
+// forward (SV = false) the ReLU words alone
+template <int l, bool TR, bool SV>
 __device__ __forceinline__ void layer(const ChainFwdArgs& p, State& st) {
     using Y = LY<TR>;
     constexpr int ntj = L_OUT[l] / 16;
@@ -1495,7 +1504,7 @@ __device__ __forceinline__ void layer(const ChainFwdArgs& p, State& st) {
     constexpr bool last_tr = TR && l == CNL - 1;
 #pragma unroll
     for (int j = 0; j < 16; ++j) st.acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    ksteps<l, 0, TR>(p, st);
+    ksteps<l, 0, TR, SV>(p, st);
     tick(p, st, nullptr);
     // the lane's feature offset, opaque per layer: otherwise the exponent / bias addresses of
     // the even (odd) layers are computed once and kept live -- spilled -- across the chain
@@ -1534,8 +1543,7 @@ __device__ __forceinline__ void layer(const ChainFwdArgs& p, State& st) {
             r = max3abs(max3abs(r, x[0], x[1]), x[2], x[3]);
         }
         if constexpr (last_tr) {   // hr (the f32 epilogue value, as the per-layer kernel) and its ReLU words
-            const nerf_chain_layer& L = p.L[l];
-            tile_store4<128>(L.out + st.m0 * 128, (fresh(st.rl) * 128 + g4) * 4, 64 * j, x);
+            if constexpr (SV) tile_store4<128>(p.L[l].out + st.m0 * 128, (fresh(st.rl) * 128 + g4) * 4, 64 * j, x);
             mw |= ((x[0] > 0.f ? 1u : 0u) | (x[1] > 0.f ? 2u : 0u) | (x[2] > 0.f ? 4u : 0u) | (x[3] > 0.f ? 8u : 0u))
                   << ((j & 1) * 16 + g4);
             if (j & 1) {
@@ -1688,18 +1696,18 @@ __device__ __forceinline__ void init_state(State& st, char* smem) {
     if (st.wave >= 4) __builtin_amdgcn_s_setprio(1);
 }
 
-template <bool TR>
+template <bool TR, bool SV = TR>
 __device__ __forceinline__ void chain_layers(const ChainFwdArgs& p, State& st) {
-    layer<0, TR>(p, st);
-    layer<1, TR>(p, st);
-    layer<2, TR>(p, st);
-    layer<3, TR>(p, st);
-    layer<4, TR>(p, st);
-    layer<5, TR>(p, st);
-    layer<6, TR>(p, st);
-    layer<7, TR>(p, st);
-    layer<8, TR>(p, st);
-    layer<9, TR>(p, st);
+    layer<0, TR, SV>(p, st);
+    layer<1, TR, SV>(p, st);
+    layer<2, TR, SV>(p, st);
+    layer<3, TR, SV>(p, st);
+    layer<4, TR, SV>(p, st);
+    layer<5, TR, SV>(p, st);
+    layer<6, TR, SV>(p, st);
+    layer<7, TR, SV>(p, st);
+    layer<8, TR, SV>(p, st);
+    layer<9, TR, SV>(p, st);
 }
 
 }  // namespace f2
@@ -1754,10 +1762,15 @@ __global__ __launch_bounds__(512, 2) void k_render_fused2(ChainFwdArgs p) {
 // HBM anyway), saving what the per-layer kernels save -- every layer's output, the ReLU
 // words, the per-128-row-group column maxima -- and raw4 from the in-epilogue heads.  The
 // stores ride beside the MFMAs and are counted in the k-steps' vmcnt waits (wait_n).
-__global__ __launch_bounds__(512, 2) void k_mlp_chain_train2(ChainFwdArgs p) {
+//
+// SV = false is the frozen-field forward (nerf_mlp_chain_frozen, k_mlp_chain_frozen): the same
+// arithmetic, LDS map and schedule with the output stores, the column maxima (their DPP
+// reductions, LDS atomics and stores) compiled out and the wait counts lowered to match -- a
+// render whose backward reaches only the rays needs the ReLU words and raw4.
+template <bool SV>
+__device__ __forceinline__ void chain_train_body(const ChainFwdArgs& p, char* smem) {
     using namespace f2;
     using Y = LY<true>;
-    __shared__ __attribute__((aligned(16))) char smem[Y::BYTES];
     State st;
     init_state<true>(st, smem);
     // l0's A operand straight from HBM, before any LDS-DMA is in flight (the compiler waits
@@ -1773,7 +1786,8 @@ __global__ __launch_bounds__(512, 2) void k_mlp_chain_train2(ChainFwdArgs p) {
     if (st.tid < 256) st.fx[FX_WD + st.tid] = p.wd[st.tid];
     for (int e = st.tid; e < 384; e += NTH) st.fx[FX_WC + e] = p.wc[e];
     // both column-max parities (512 words) and both ReLU-word parities (2048 words) cleared
-    for (int e = st.tid; e < cm_words(CMQ_FWD); e += NTH) reinterpret_cast<uint32_t*>(smem + Y::O_CMX)[e] = 0u;
+    if constexpr (SV)
+        for (int e = st.tid; e < cm_words(CMQ_FWD); e += NTH) reinterpret_cast<uint32_t*>(smem + Y::O_CMX)[e] = 0u;
     static_assert(2 * 128 * MSKW == 4 * NTH, "one uint4 per thread");
     reinterpret_cast<uint4*>(smem + Y::O_MSK)[st.tid] = make_uint4(0u, 0u, 0u, 0u);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1781,7 +1795,7 @@ __global__ __launch_bounds__(512, 2) void k_mlp_chain_train2(ChainFwdArgs p) {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_prologue<true>()) : "memory");
     __syncthreads();   // B_0
     tick(p, st, &st.t_pro);
-    chain_layers<true>(p, st);
+    chain_layers<true, SV>(p, st);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();   // every row's raw4 in LDS, lf's column maxima complete
     write_stamps(p, st);
@@ -1790,9 +1804,17 @@ __global__ __launch_bounds__(512, 2) void k_mlp_chain_train2(ChainFwdArgs p) {
     const size_t m0 = (size_t)blockIdx.x * CROWS;
     if (tid < CROWS)
         *reinterpret_cast<float4*>(p.raw4 + (m0 + tid) * 4) = *reinterpret_cast<const float4*>(st.fx + FX_RAW + 4 * tid);
-    else if (tid < CROWS + 256)
+    else if (SV && tid < CROWS + 256)
         p.L[8].cmax[(m0 / CROWS) * L_OUT[8] + tid - CROWS] =
             __uint_as_float(cm_read<CMQ_FWD>(reinterpret_cast<const uint32_t*>(smem + Y::O_CMX), (8 & 1) * 256 + tid - CROWS));
+}
+__global__ __launch_bounds__(512, 2) void k_mlp_chain_train2(ChainFwdArgs p) {
+    __shared__ __attribute__((aligned(16))) char smem[f2::LY<true>::BYTES];
+    chain_train_body<true>(p, smem);
+}
+__global__ __launch_bounds__(512, 2) void k_mlp_chain_frozen(ChainFwdArgs p) {
+    __shared__ __attribute__((aligned(16))) char smem[f2::LY<true>::BYTES];
+    chain_train_body<false>(p, smem);
 }
 
 // ---------------------------------------------------------------------------
@@ -1847,34 +1869,48 @@ constexpr int dma_step(int m) { return m >= NK ? 0 : dma_count(tt_of_k(m)) + dma
 constexpr int dma_in(int j) { return dma_step(j + NPAIR - 1); }
 // stores of step k before its barrier: the D_i pair stores (pairs 0 and 1 at u = 0, pair u + 1
 // at u = 1 .. nks - 2), at a layer's first step the previous dy's column maxima; behind its
-// DMAs (post): at a layer's last step the epilogue's row-max store
+// DMAs (post): at a layer's last step the epilogue's row-max store.
+// RY = true (the ray-gradient chain, k_mlp_chain_bwd_rays): only D_0 and D_5 are stored by
+// k-steps (D_9 by the last epilogue), no column maxima, and of the epilogues' row maxima only
+// D_5's (layer 4's) -- the counts drop with the stores (f2::pre_st)
+constexpr bool ry_keeps(int d) { return d == 0 || d == 5 || d == 9; }   // the D_i the ray path consumes
+template <bool RY>
 constexpr int pre_st(int k) {
     const int i = layer_of_k(k), u = k - kfirst(i);
-    return (u == 0 ? 4 : (u + 1 < nks(i) ? 2 : 0)) + (u == 0 && i >= 1 ? 1 : 0);
+    const int pairs = u == 0 ? 4 : (u + 1 < nks(i) ? 2 : 0);
+    if (RY) return ry_keeps(i) ? pairs : 0;
+    return pairs + (u == 0 && i >= 1 ? 1 : 0);
 }
+template <bool RY>
 constexpr int post_st(int k) {
     const int i = layer_of_k(k), u = k - kfirst(i);
-    return u == nks(i) - 1 && i < NL - 1 ? 1 : 0;
+    return u == nks(i) - 1 && i < NL - 1 && (!RY || ry_keeps(i + 1)) ? 1 : 0;
 }
 // the counted wait before B_{k+1} for step k + 1's DMAs, issued behind the barrier of step j0 =
 // k + 2 - NPAIR (f2::wait_n, plus the post stores)
+template <bool RY>
 constexpr int wait_n(int k) {
     const int j0 = k + 2 - NPAIR;
     int n = 0;
     if (j0 < 0)
         for (int m = k + 2; m <= NPAIR - 2; ++m) n += dma_step(m);
     else
-        n += post_st(j0);
-    for (int j = (j0 + 1 > 0 ? j0 + 1 : 0); j < k; ++j) n += pre_st(j) + dma_in(j) + post_st(j);
-    return n + pre_st(k);
+        n += post_st<RY>(j0);
+    for (int j = (j0 + 1 > 0 ? j0 + 1 : 0); j < k; ++j) n += pre_st<RY>(j) + dma_in(j) + post_st<RY>(j);
+    return n + pre_st<RY>(k);
 }
 constexpr int wait_prologue() {
     int n = 0;
     for (int m = 1; m <= NPAIR - 2; ++m) n += dma_step(m);
     return n;
 }
-static_assert(wait_n(0) == dma_step(2) + pre_st(0) && wait_prologue() == dma_step(1) + dma_step(2), "prologue waits");
-static_assert(wait_n(4) == post_st(2) + pre_st(3) + dma_in(3) + post_st(3) + pre_st(4), "waits");
+static_assert(wait_n<false>(0) == dma_step(2) + pre_st<false>(0) && wait_prologue() == dma_step(1) + dma_step(2),
+              "prologue waits");
+static_assert(wait_n<false>(4) == post_st<false>(2) + pre_st<false>(3) + dma_in(3) + post_st<false>(3) + pre_st<false>(4),
+              "waits");
+static_assert(wait_n<true>(0) == dma_step(2) + 4 && wait_n<true>(4) == pre_st<true>(3) + dma_in(3) && post_st<true>(3) == 0 &&
+                  wait_n<true>(8) == dma_in(7) && post_st<true>(kfirst(5) - 1) == 1 && pre_st<true>(kfirst(5)) == 4,
+              "ray-gradient chain waits");
 static_assert(f2::piece_tile<16>(f2::P_STORE) <= TB && f2::piece_tile<16>(f2::P0_STORE) <= TB &&
                   f2::piece_tile<16>(f2::P_STORE_B) <= TB && f2::piece_tile<16>(f2::P0_STORE_B) <= TB,
               "stores before B");
@@ -1939,9 +1975,11 @@ __device__ __forceinline__ void dma_n(const nerf_chain_bwd& p, State& st) {
 
 // D_i's save work at layer i's k-step u, piece j: pair stores and the column maxima (parity
 // i & 1) of tiles 2t, 2t + 1 (pair 0 and 1 at u = 0, pair u + 1 later)
-template <int i, int u, int j>
+// (RY: the pair stores of D_0 and D_5 only, no column maxima)
+template <int i, int u, int j, bool RY>
 __device__ __forceinline__ void save_pieces(const nerf_chain_bwd& p, State& st) {
     using f2::Piece;
+    constexpr bool ST = !RY || ry_keeps(i), CM = !RY;
     constexpr int W = i == 0 ? 128 : 256;   // D_0 = dyr is 128 wide
     constexpr int npair = W / 32;
     auto cm_at = [&](int t, int half) {
@@ -1950,21 +1988,22 @@ __device__ __forceinline__ void save_pieces(const nerf_chain_bwd& p, State& st) 
         return reinterpret_cast<uint32_t*>(st.lds + o) + (i & 1) * 256 + 32 * t + 16 * half;
     };
     const bool leader = (st.n & (16 / CMQ - 1)) == 0;
-    float* ob = p.dy[i] + st.m0 * W;
+    float* ob = ST ? p.dy[i] + st.m0 * W : nullptr;
     int vrow = st.vrow;
     if constexpr (W != 256) vrow = (st.rl * W + 4 * st.g) * 4;
     if constexpr (u == 0) {
-        if constexpr (j == piece_tile<16>(f2::P0_STORE)) f2::tile_store4<W>(ob, vrow, 0, st.xs[0]);
-        if constexpr (j == piece_tile<16>(f2::P0_STORE_B)) f2::tile_store4<W>(ob, vrow, 64, st.xs[1]);
-        if constexpr (j == piece_tile<16>(f2::P0_CMAX_A)) f2::colmax4<CMQ>(st.xs[0], cm_at(0, 0), leader);
-        if constexpr (j == piece_tile<16>(f2::P0_CMAX_B)) f2::colmax4<CMQ>(st.xs[1], cm_at(0, 1), leader);
+        if constexpr (ST && j == piece_tile<16>(f2::P0_STORE)) f2::tile_store4<W>(ob, vrow, 0, st.xs[0]);
+        if constexpr (ST && j == piece_tile<16>(f2::P0_STORE_B)) f2::tile_store4<W>(ob, vrow, 64, st.xs[1]);
+        if constexpr (CM && j == piece_tile<16>(f2::P0_CMAX_A)) f2::colmax4<CMQ>(st.xs[0], cm_at(0, 0), leader);
+        if constexpr (CM && j == piece_tile<16>(f2::P0_CMAX_B)) f2::colmax4<CMQ>(st.xs[1], cm_at(0, 1), leader);
     }
     if constexpr (u + 1 < npair) {
         constexpr int t = u + 1;
-        if constexpr (j == piece_tile<16>(f2::P_STORE)) f2::tile_store4<W>(ob, vrow, 128 * t, st.xs[2 * t]);
-        if constexpr (j == piece_tile<16>(f2::P_STORE_B)) f2::tile_store4<W>(ob, vrow, 128 * t + 64, st.xs[2 * t + 1]);
-        if constexpr (j == piece_tile<16>(f2::P_CMAX_A)) f2::colmax4<CMQ>(st.xs[2 * t], cm_at(t, 0), leader);
-        if constexpr (j == piece_tile<16>(f2::P_CMAX_B)) f2::colmax4<CMQ>(st.xs[2 * t + 1], cm_at(t, 1), leader);
+        if constexpr (ST && j == piece_tile<16>(f2::P_STORE)) f2::tile_store4<W>(ob, vrow, 128 * t, st.xs[2 * t]);
+        if constexpr (ST && j == piece_tile<16>(f2::P_STORE_B))
+            f2::tile_store4<W>(ob, vrow, 128 * t + 64, st.xs[2 * t + 1]);
+        if constexpr (CM && j == piece_tile<16>(f2::P_CMAX_A)) f2::colmax4<CMQ>(st.xs[2 * t], cm_at(t, 0), leader);
+        if constexpr (CM && j == piece_tile<16>(f2::P_CMAX_B)) f2::colmax4<CMQ>(st.xs[2 * t + 1], cm_at(t, 1), leader);
     }
 }
 
@@ -2017,13 +2056,13 @@ __device__ __forceinline__ void frag_reads(State& st) {
 // behind layer i's first tile: its weight-row exponents (landed with the step) as the scales
 // 2^-e for its epilogue; D_{i-1}'s column maxima (complete since layer i-1's last step) out and
 // cleared -- D_0 is 128 wide: waves 4-7 store theirs to the scratch row (one store op per wave)
-template <int i>
+template <int i, bool RY>
 __device__ __forceinline__ void layer_start(const nerf_chain_bwd& p, State& st) {
     const int tid = f2::fresh(st.tid);
     if (tid < 256)
         reinterpret_cast<float*>(st.lds + O_EXP)[(i & 1) * 256 + tid] = __builtin_amdgcn_ldexpf(
             1.f, -reinterpret_cast<const int*>(st.lds + O_LEB + (i & 1) * 1024)[tid]);
-    if constexpr (i >= 1) {
+    if constexpr (i >= 1 && !RY) {
         constexpr int W = i - 1 == 0 ? 128 : 256;
         const int lane = tid & 63;
         if (lane < 32) {
@@ -2037,7 +2076,7 @@ __device__ __forceinline__ void layer_start(const nerf_chain_bwd& p, State& st) 
     }
 }
 
-template <int i, int u, int j>
+template <int i, int u, int j, bool RY>
 __device__ __forceinline__ void tiles(const nerf_chain_bwd& p, State& st, const uint4& ah, const uint4& al) {
     constexpr int R = PF + 1;
     constexpr int k = kfirst(i) + u, G = 16 * k + j;
@@ -2047,44 +2086,44 @@ __device__ __forceinline__ void tiles(const nerf_chain_bwd& p, State& st, const 
         st.acc[j] = f2::mfma16(st.wh[G % R], al, st.acc[j]);   // hi . lo
         st.acc[j] = f2::mfma16(st.wl[G % R], ah, st.acc[j]);   // lo . hi
         st.acc[j] = f2::mfma16(st.wh[G % R], ah, st.acc[j]);   // hi . hi
-        if constexpr (u == 0 && j == 0) layer_start<i>(p, st);
+        if constexpr (u == 0 && j == 0) layer_start<i, RY>(p, st);
         split_pieces<i, u, j>(st);
-        save_pieces<i, u, j>(p, st);
+        save_pieces<i, u, j, RY>(p, st);
         if constexpr (k + 1 < NK && j == TB) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_n(k)) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_n<RY>(k)) : "memory");
             __syncthreads();   // B_{k+1}
             dma<tt_of_k(k + NPAIR - 1)>(p, st);
         }
         if constexpr (k + 1 < NK && j == TB + f2::DMA2) dma<tt_of_k(k + NPAIR - 1) + 1>(p, st);
         __builtin_amdgcn_sched_barrier(0);
-        tiles<i, u, j + 1>(p, st, ah, al);
+        tiles<i, u, j + 1, RY>(p, st, ah, al);
     }
 }
 
-template <int i, int u>
+template <int i, int u, bool RY>
 __device__ __forceinline__ void kstep(const nerf_chain_bwd& p, State& st) {
     if constexpr (u == 0) frag_reads<16 * kfirst(i), PF>(st);
-    tiles<i, u, 0>(p, st, st.act_hi[u], st.act_lo[u]);
+    tiles<i, u, 0, RY>(p, st, st.act_hi[u], st.act_lo[u]);
 }
 
-template <int i, int u>
+template <int i, int u, bool RY>
 __device__ __forceinline__ void ksteps(const nerf_chain_bwd& p, State& st) {
     if constexpr (u < nks(i)) {
-        kstep<i, u>(p, st);
-        ksteps<i, u + 1>(p, st);
+        kstep<i, u, RY>(p, st);
+        ksteps<i, u + 1, RY>(p, st);
     }
 }
 
 // layer i: k-loop, then the epilogue -- unscale, the feature layer's rank-one term, the
 // input's ReLU mask -> D_{i+1} (features 16 j + 4 g + c of the lane's row, tile layout), its
 // row max and k-step 0's A fragment (the rest during the next layer's k-steps); the last
-// layer stores D_9 and its column maxima here
-template <int i>
+// layer stores D_9 and its column maxima here (RY: D_9 alone, and only D_5's and D_9's row maxima)
+template <int i, bool RY>
 __device__ __forceinline__ void layer(const nerf_chain_bwd& p, State& st) {
     constexpr bool last = i == NL - 1;
 #pragma unroll
     for (int j = 0; j < 16; ++j) st.acc[j] = f2::f32x4{0.f, 0.f, 0.f, 0.f};
-    ksteps<i, 0>(p, st);
+    ksteps<i, 0, RY>(p, st);
     int g4 = 4 * st.g;
     asm volatile("" : "+v"(g4));
     const float* le = reinterpret_cast<const float*>(st.lds + O_EXP) + (i & 1) * 256 + g4;
@@ -2103,14 +2142,22 @@ __device__ __forceinline__ void layer(const nerf_chain_bwd& p, State& st) {
         __builtin_amdgcn_sched_barrier(0);
         const int f0 = 16 * j + g4;
         const float4 s4 = *reinterpret_cast<const float4*>(le + 16 * j);
-        const f2::pf2 x01 = (f2::pf2{st.acc[j][0], st.acc[j][1]} * sr2) * f2::pf2{s4.x, s4.y};
-        const f2::pf2 x23 = (f2::pf2{st.acc[j][2], st.acc[j][3]} * sr2) * f2::pf2{s4.z, s4.w};
+        const f2::pf2 a01 = f2::pf2{st.acc[j][0], st.acc[j][1]} * sr2, a23 = f2::pf2{st.acc[j][2], st.acc[j][3]} * sr2;
+        f2::pf2 x01, x23;
+        if constexpr (i == 1) {
+            // + d sigma_raw x w_density (the density head reads h7): the rounded product joins the
+            // weight-row scaling in one fma.  Written out: left to the compiler's contraction of
+            // (a s) + (g w), k_mlp_chain_bwd fused the scaling (this form) and k_mlp_chain_bwd_rays
+            // the product, and their D_2 .. D_9 differed in the last bit
+            const float4 w4 = *reinterpret_cast<const float4*>(st.fx + f0);
+            x01 = __builtin_elementwise_fma(a01, f2::pf2{s4.x, s4.y}, f2::pf2{st.gr0 * w4.x, st.gr0 * w4.y});
+            x23 = __builtin_elementwise_fma(a23, f2::pf2{s4.z, s4.w}, f2::pf2{st.gr0 * w4.z, st.gr0 * w4.w});
+        } else {
+            x01 = a01 * f2::pf2{s4.x, s4.y};
+            x23 = a23 * f2::pf2{s4.z, s4.w};
+        }
         f2::f32x4 x;
         x[0] = x01[0]; x[1] = x01[1]; x[2] = x23[0]; x[3] = x23[1];
-        if constexpr (i == 1) {   // + d sigma_raw x w_density (the density head reads h7)
-            const float4 w4 = *reinterpret_cast<const float4*>(st.fx + f0);
-            x[0] += st.gr0 * w4.x; x[1] += st.gr0 * w4.y; x[2] += st.gr0 * w4.z; x[3] += st.gr0 * w4.w;
-        }
         if constexpr (i >= 1) {   // the input's ReLU bits: all-ones / zero masks by a signed bit extract
             const uint32_t bits = mw[j >> 1] >> ((j & 1) * 16 + g4);
 #pragma unroll
@@ -2125,7 +2172,9 @@ __device__ __forceinline__ void layer(const nerf_chain_bwd& p, State& st) {
         }
         if constexpr (last) {
             f2::tile_store4<256>(p.dy[NL] + st.m0 * 256, st.vrow, 64 * j, x);
-            if constexpr (CMQ == 1)
+            if constexpr (RY) {
+                // no column maxima
+            } else if constexpr (CMQ == 1)
                 f2::colmax4(x, reinterpret_cast<uint32_t*>(st.lds + O_CMX) + (NL & 1) * 256 + f0, st.n == 0);
             else
                 f2::colmax4<CMQ>(x, reinterpret_cast<uint32_t*>(st.lds + O_CMX + 16 * st.g +
@@ -2136,7 +2185,9 @@ __device__ __forceinline__ void layer(const nerf_chain_bwd& p, State& st) {
     }
     // the row's max over its four 16-lane rows (lanes n, n + 16, n + 32, n + 48)
     const float m = f2::rows_max(rmx);
-    if (st.g == 0) p.dy_rmax[i + 1][st.m0 + f2::fresh(st.rl)] = m;
+    if constexpr (!RY || ry_keeps(i + 1)) {
+        if (st.g == 0) p.dy_rmax[i + 1][st.m0 + f2::fresh(st.rl)] = m;
+    }
     if constexpr (!last) {
         st.er = f2::chain_exp(m);
         st.ser = __builtin_amdgcn_ldexpf(1.f, st.er);
@@ -2145,24 +2196,28 @@ __device__ __forceinline__ void layer(const nerf_chain_bwd& p, State& st) {
     }
 }
 
+template <bool RY>
 __device__ __forceinline__ void layers(const nerf_chain_bwd& p, State& st) {
-    layer<0>(p, st);
-    layer<1>(p, st);
-    layer<2>(p, st);
-    layer<3>(p, st);
-    layer<4>(p, st);
-    layer<5>(p, st);
-    layer<6>(p, st);
-    layer<7>(p, st);
-    layer<8>(p, st);
+    layer<0, RY>(p, st);
+    layer<1, RY>(p, st);
+    layer<2, RY>(p, st);
+    layer<3, RY>(p, st);
+    layer<4, RY>(p, st);
+    layer<5, RY>(p, st);
+    layer<6, RY>(p, st);
+    layer<7, RY>(p, st);
+    layer<8, RY>(p, st);
 }
 
 }  // namespace b2
 
-__global__ __launch_bounds__(512, 2) void k_mlp_chain_bwd(ChainBwdArgs args) {
+// RY = true is the ray-gradient chain (nerf_mlp_chain_bwd_rays, k_mlp_chain_bwd_rays): the same
+// arithmetic, LDS map and schedule, storing only what the ray gradients read -- D_0, D_5, D_9 and
+// their row maxima (the A operands of the three 64-wide encoding-gradient GEMMs) -- with the
+// other seven D_i stores and every column maximum compiled out.
+template <bool RY>
+__device__ __forceinline__ void chain_bwd_body(const nerf_chain_bwd& p, char* smem) {
     using namespace b2;
-    const nerf_chain_bwd& p = args.a;
-    __shared__ __attribute__((aligned(16))) char smem[BYTES];
     State st;
     st.lds = smem;
     st.lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(clds_t*)smem);
@@ -2179,7 +2234,8 @@ __global__ __launch_bounds__(512, 2) void k_mlp_chain_bwd(ChainBwdArgs args) {
     // head weights into LDS, both column-max parities cleared
     if (st.tid < 256) st.fx[st.tid] = p.wd[st.tid];
     for (int e = st.tid; e < 384; e += NTH) st.fx[256 + e] = p.wc[e];
-    for (int e = st.tid; e < f2::cm_words(CMQ); e += NTH) reinterpret_cast<uint32_t*>(smem + O_CMX)[e] = 0u;
+    if constexpr (!RY)
+        for (int e = st.tid; e < f2::cm_words(CMQ); e += NTH) reinterpret_cast<uint32_t*>(smem + O_CMX)[e] = 0u;
     const size_t row = st.m0 + st.rl;
     const float4 gr = *reinterpret_cast<const float4*>(p.graw4 + row * 4);
     const uint4 mr = *reinterpret_cast<const uint4*>(p.hr_mask + row * p.ld_hr_mask);
@@ -2209,17 +2265,27 @@ __global__ __launch_bounds__(512, 2) void k_mlp_chain_bwd(ChainBwdArgs args) {
     dma_n<0, 2 * (NPAIR - 1)>(p, st);   // steps 0 .. NPAIR - 2
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_prologue()) : "memory");
     __syncthreads();   // B_0
-    layers(p, st);
+    layers<RY>(p, st);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    // D_8's (parity 0, saved by layer 8's k-steps) and D_9's (parity 1, the last epilogue)
-    // column maxima
-    int tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    const size_t grp = (size_t)blockIdx.x;
-    const int par = tid >> 8, f = tid & 255;
-    p.dy_cmax[NL - 1 + par][grp * 256 + f] =
-        __uint_as_float(f2::cm_read<CMQ>(reinterpret_cast<const uint32_t*>(smem + O_CMX), tid));
+    if constexpr (!RY) {
+        // D_8's (parity 0, saved by layer 8's k-steps) and D_9's (parity 1, the last epilogue)
+        // column maxima
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const size_t grp = (size_t)blockIdx.x;
+        const int par = tid >> 8, f = tid & 255;
+        p.dy_cmax[NL - 1 + par][grp * 256 + f] =
+            __uint_as_float(f2::cm_read<CMQ>(reinterpret_cast<const uint32_t*>(smem + O_CMX), tid));
+    }
+}
+__global__ __launch_bounds__(512, 2) void k_mlp_chain_bwd(ChainBwdArgs args) {
+    __shared__ __attribute__((aligned(16))) char smem[b2::BYTES];
+    chain_bwd_body<false>(args.a, smem);
+}
+__global__ __launch_bounds__(512, 2) void k_mlp_chain_bwd_rays(ChainBwdArgs args) {
+    __shared__ __attribute__((aligned(16))) char smem[b2::BYTES];
+    chain_bwd_body<true>(args.a, smem);
 }
 }  // namespace nerf
 
@@ -2294,6 +2360,47 @@ extern "C" int nerf_mlp_chain_train(const float* enc_p, const float* enc_d, cons
     prof_next(NERF_PROF_CHAIN_FWD, rows * (2 * 64 * 4 + 9 * 256 * 4 + 128 * 4 + 9 * 32 + 4 * 4));
     prof_begin(as_stream(stream));
     hipLaunchKernelGGL(k_mlp_chain_train2, dim3(n_pad / CROWS), dim3(f2::NTH), 0, as_stream(stream), a);
+    prof_end(as_stream(stream), 2.0 * rows * (256.0 * 63 + 7 * 256 * 256 + 256 * 319 + 128 * 283 + 256 + 3 * 128), 3);
+    return check_launch(__func__);
+}
+
+extern "C" int nerf_mlp_chain_frozen(const float* enc_p, const float* enc_d, const float* enc_p_rmax,
+                                     const float* enc_d_rmax, int n_pad, const nerf_chain_layer* layers, const float* wd,
+                                     const float* bd, const float* wc, const float* bc, float* raw4, void* stream) {
+    NERF_CHECK_PTR(enc_p); NERF_CHECK_PTR(enc_d); NERF_CHECK_PTR(enc_p_rmax); NERF_CHECK_PTR(enc_d_rmax);
+    NERF_CHECK_PTR(layers); NERF_CHECK_PTR(wd); NERF_CHECK_PTR(bd); NERF_CHECK_PTR(wc); NERF_CHECK_PTR(bc);
+    NERF_CHECK_PTR(raw4);
+    NERF_CHECK(n_pad > 0 && n_pad % CROWS == 0, "%s: n_pad=%d must be a positive multiple of %d", __func__, n_pad,
+               CROWS);
+    // the kernel has no output or column-maximum stores: a pointer given here would stay unwritten
+    for (int l = 0; l < CNL; ++l)
+        NERF_CHECK(layers[l].out == nullptr && layers[l].cmax == nullptr,
+                   "%s: layer %d: the frozen-field chain saves no layer output and no column maxima (out and cmax "
+                   "must be NULL)", __func__, l);
+    NERF_CHECK(gemm_precision() == 2, "%s: the fused chain runs in GEMM precision mode 2 (fp16 pair images)", __func__);
+    NERF_CHECK_ALIGN16(enc_p); NERF_CHECK_ALIGN16(enc_d); NERF_CHECK_ALIGN16(raw4);
+    ChainFwdArgs a{};
+    a.enc_p = enc_p; a.enc_d = enc_d; a.rp = enc_p_rmax; a.rd = enc_d_rmax; a.n_pad = n_pad;
+    for (int l = 0; l < CNL; ++l) {
+        const nerf_chain_layer& L = layers[l];
+        NERF_CHECK(L.img && L.bias, "%s: layer %d needs its weight image and bias", __func__, l);
+        NERF_CHECK((((uintptr_t)L.bias) & 15u) == 0 && (((uintptr_t)L.img) & 15u) == 0 && L.img_rows == L_OUT[l],
+                   "%s: layer %d: image / bias not 16-byte aligned or chain image rows %d != %d", __func__, l,
+                   L.img_rows, L_OUT[l]);
+        // the ReLU-word stores are counted in the k-steps' vmcnt waits at compile time
+        NERF_CHECK(l == 8 || (L.mask && L.ldmask >= L_OUT[l] / 32 && L.ldmask % 2 == 0 &&
+                              (((uintptr_t)L.mask) & 7u) == 0),
+                   "%s: layer %d: the ReLU words are mandatory (ldmask %d, even, 8-byte aligned)", __func__, l, L.ldmask);
+        NERF_CHECK(l != 8 || L.mask == nullptr, "%s: the feature layer has no ReLU", __func__);
+        a.L[l] = L;
+    }
+    a.wd = wd; a.bd = bd; a.wc = wc; a.bc = bc; a.raw4 = raw4;
+    a.stamps = g_chain_stamps;
+    // the work of nerf_mlp_chain_train; HBM: the two encodings read, the ReLU words and raw4 written
+    const double rows = (double)n_pad;
+    prof_next(NERF_PROF_CHAIN_FWD, rows * (2 * 64 * 4 + 9 * 32 + 4 * 4));
+    prof_begin(as_stream(stream));
+    hipLaunchKernelGGL(k_mlp_chain_frozen, dim3(n_pad / CROWS), dim3(f2::NTH), 0, as_stream(stream), a);
     prof_end(as_stream(stream), 2.0 * rows * (256.0 * 63 + 7 * 256 * 256 + 256 * 319 + 128 * 283 + 256 + 3 * 128), 3);
     return check_launch(__func__);
 }
@@ -2375,6 +2482,48 @@ extern "C" int nerf_mlp_chain_bwd(const nerf_chain_bwd* a, void* stream) {
     prof_next(NERF_PROF_CHAIN_BWD, rows * (16 + 16 + 8 * 32 + 128 * 4 + 9 * 256 * 4 + 10 * 4));
     prof_begin(as_stream(stream));
     hipLaunchKernelGGL(k_mlp_chain_bwd, dim3(p.n_pad / CROWS), dim3(f2::NTH), 0, as_stream(stream), args);
+    prof_end(as_stream(stream), 2.0 * rows * (3.0 * 128 + 128 * 256 + 8 * 256 * 256), 3);
+    return check_launch(__func__);
+}
+
+extern "C" int nerf_mlp_chain_bwd_rays(const nerf_chain_bwd* a, void* stream) {
+    NERF_CHECK_PTR(a);
+    const nerf_chain_bwd& p = *a;
+    NERF_CHECK(p.n_pad > 0 && p.n_pad % CROWS == 0, "%s: n_pad=%d must be a positive multiple of %d", __func__,
+               p.n_pad, CROWS);
+    // only D_0, D_5 and D_9 leave the kernel, with their row maxima and no column maxima: any
+    // other pointer given here would stay unwritten
+    for (int i = 0; i < 10; ++i) {
+        const int w = i == 0 ? 128 : 256;
+        if (b2::ry_keeps(i))
+            NERF_CHECK(p.dy[i] && p.lddy[i] == w && (((uintptr_t)p.dy[i]) & 15u) == 0 && p.dy_rmax[i] && !p.dy_cmax[i],
+                       "%s: D_%d: output and row maxima are mandatory (ld == %d, 16-byte aligned), column maxima "
+                       "are not written (dy_cmax must be NULL)", __func__, i, w);
+        else
+            NERF_CHECK(!p.dy[i] && !p.dy_cmax[i] && !p.dy_rmax[i],
+                       "%s: D_%d is not stored by the ray-gradient chain (dy, dy_cmax and dy_rmax must be NULL)",
+                       __func__, i);
+    }
+    NERF_CHECK(gemm_precision() == 2, "%s: the chain runs in GEMM precision mode 2 (fp16 pair images)", __func__);
+    NERF_CHECK(p.graw4 && p.hr_mask && p.ld_hr_mask >= 4 && p.wd && p.wc,
+               "%s: graw4, the colour layer's ReLU words (ld >= 4), wd and wc are required", __func__);
+    NERF_CHECK_ALIGN16(p.graw4); NERF_CHECK_ALIGN16(p.wd);
+    NERF_CHECK((((uintptr_t)p.hr_mask) & 15u) == 0 && p.ld_hr_mask % 4 == 0, "%s: hr_mask 16-byte rows", __func__);
+    for (int i = 0; i < 9; ++i) {
+        NERF_CHECK(p.wt_img[i] && (((uintptr_t)p.wt_img[i]) & 15u) == 0 && p.wt_img_rows[i] == b2::KPB[i],
+                   "%s: layer %d: weight-transpose chain image missing, unaligned or not %d rows", __func__, i,
+                   b2::KPB[i]);
+        NERF_CHECK(i == 0 || (p.in_mask[i] && p.ld_in_mask[i] >= 8 && (((uintptr_t)p.in_mask[i]) & 15u) == 0 &&
+                              p.ld_in_mask[i] % 4 == 0),
+                   "%s: layer %d: the input's ReLU words (ld >= 8, 16-byte rows) are required", __func__, i);
+    }
+    ChainBwdArgs args{p};
+    // the work of nerf_mlp_chain_bwd; HBM: graw4 and the ReLU words read, D_0, D_5, D_9 (f32) and
+    // their row maxima written
+    const double rows = (double)p.n_pad;
+    prof_next(NERF_PROF_CHAIN_BWD, rows * (16 + 16 + 8 * 32 + 128 * 4 + 2 * 256 * 4 + 3 * 4));
+    prof_begin(as_stream(stream));
+    hipLaunchKernelGGL(k_mlp_chain_bwd_rays, dim3(p.n_pad / CROWS), dim3(f2::NTH), 0, as_stream(stream), args);
     prof_end(as_stream(stream), 2.0 * rows * (3.0 * 128 + 128 * 256 + 8 * 256 * 256), 3);
     return check_launch(__func__);
 }

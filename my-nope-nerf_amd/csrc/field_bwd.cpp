@@ -574,3 +574,100 @@ int schedule(const nerf_field_bwd& a, void* stream, void* side_stream) {
     return NERF_OK;
 }
 }  // namespace
+
+// ---------------------------------------------------------------------------
+// The ray-gradient-only backward of a frozen field (nerf_field_backward_rays): the part of
+// chain_schedule that reaches pts_o / pts_d / view, for a step that optimises only what
+// produces the rays (test-time pose refinement: eval_pose_one_epoch.py:30-76 steps
+// optimizer_pose alone).  No weight gradient, slab reduce or head-weight partial runs, so
+// nothing reads a saved layer output or a column maximum: the chain stores only the three dy
+// the encoding segments read and everything is on the caller's stream.
+namespace {
+
+struct RaysWork {
+    float *graw4, *d0, *d5, *d9, *rm0, *rm5, *rm9, *genc_p0, *genc_p4, *genc_d;
+};
+
+size_t carve_rays(char* base, int np, RaysWork& w) {
+    Carve c{base};
+    w.graw4 = c.take((size_t)np * 4);
+    w.d0 = c.take((size_t)np * HR);
+    w.d5 = c.take((size_t)np * D);
+    w.d9 = c.take((size_t)np * D);
+    w.rm0 = c.take(np);
+    w.rm5 = c.take(np);
+    w.rm9 = c.take(np);
+    w.genc_p0 = c.take((size_t)np * 64);
+    w.genc_p4 = c.take((size_t)np * 64);
+    w.genc_d = c.take((size_t)np * 64);
+    return c.off + 256;
+}
+
+}  // namespace
+
+extern "C" size_t nerf_field_bwd_rays_workspace_bytes(int n_pad) {
+    if (n_pad <= 0 || n_pad % 128) return 0;
+    RaysWork w;
+    return carve_rays(nullptr, n_pad, w);
+}
+
+extern "C" int nerf_field_backward_rays(const nerf_field_bwd_rays* ap, void* stream) {
+    NERF_CHECK_PTR(ap);
+    const nerf_field_bwd_rays& a = *ap;
+    const int np = a.n_pad;
+    NERF_CHECK(np > 0 && np % 128 == 0 && a.workspace, "%s: n_pad=%d (a positive multiple of 128) and a workspace "
+               "(nerf_field_bwd_rays_workspace_bytes) are required", __func__, np);
+    NERF_CHECK(nerf::gemm_precision() == 2, "%s: the native backward runs GEMM precision mode 2", __func__);
+    NERF_CHECK(a.graw4 || (a.g_rgb && a.g_dist && a.raw4), "%s: need graw4 or (g_rgb, g_dist, raw4)", __func__);
+    for (int l = 0; l < L; ++l) {
+        NERF_CHECK(l == 0 || a.wt_cimg[l], "%s: layer %d: the input-gradient chain needs the chain image of W^T "
+                   "(wt_cimg)", __func__, l);
+        NERF_CHECK((l == LF) == (a.mask[l] == nullptr), "%s: layer %d: ReLU words (none for the feature layer)",
+                   __func__, l);
+    }
+    for (int l : {0, 4, LR})
+        NERF_CHECK(a.wt[l] && a.wt_img[l], "%s: layer %d: W^T and its fp16 pair image (the encoding rows' operand)",
+                   __func__, l);
+    NERF_CHECK(a.wd && a.wc, "%s: missing head weights", __func__);
+    NERF_CHECK(a.pts_o && a.pts_d && a.view && a.z && a.g_pts_o && a.g_pts_d && a.g_view,
+               "%s: pts_o / pts_d / view / z and the three gradient outputs are required", __func__);
+    RaysWork w;
+    carve_rays(reinterpret_cast<char*>(a.workspace), np, w);
+
+    const float* graw4 = a.graw4;
+    if (!graw4) {
+        RC(nerf_composite_bwd(a.raw4, a.z, a.n_rays, a.n_samples, a.flags, a.g_rgb, a.g_dist, w.graw4, np, stream));
+        graw4 = w.graw4;
+    }
+    nerf_chain_bwd c{};
+    c.graw4 = graw4;
+    c.hr_mask = a.mask[LR];
+    c.ld_hr_mask = HR / 32;
+    c.wd = a.wd;
+    c.wc = a.wc;
+    for (int i = 0; i < 9; ++i) {
+        const int l = LR - i;
+        c.wt_img[i] = a.wt_cimg[l];
+        c.wt_img_rows[i] = KP[l];
+        c.in_mask[i] = l == LR ? nullptr : a.mask[l - 1];
+        c.ld_in_mask[i] = OUT_P[l - 1 < 0 ? 0 : l - 1] / 32;
+    }
+    // D_0 = dyr, D_5 the gradient at l4's output, D_9 at l0's
+    c.dy[0] = w.d0; c.lddy[0] = HR; c.dy_rmax[0] = w.rm0;
+    c.dy[5] = w.d5; c.lddy[5] = D; c.dy_rmax[5] = w.rm5;
+    c.dy[9] = w.d9; c.lddy[9] = D; c.dy_rmax[9] = w.rm9;
+    c.n_pad = np;
+    RC(nerf_mlp_chain_bwd_rays(&c, stream));
+    // the encoding rows of W^T against a layer's dy (chain_schedule's enc_rows)
+    auto enc_rows = [&](int l, const float* dy, const float* rm, float* out) -> int {
+        const int op = OUT_P[l];
+        const int k0 = l == 0 ? 0 : K1[l];
+        return nerf_linear_bwd_data(dy, op, op, a.wt[l] + (size_t)k0 * op, a.wt_img[l] + (size_t)k0 * 8, KP[l], nullptr, 0,
+                                    nullptr, nullptr, 0, out, 64, np, 64, rm, nullptr, nullptr, stream);
+    };
+    RC(enc_rows(LR, w.d0, w.rm0, w.genc_d));
+    RC(enc_rows(4, w.d5, w.rm5, w.genc_p4));
+    RC(enc_rows(0, w.d9, w.rm9, w.genc_p0));
+    return nerf_encode_bwd(a.pts_o, a.pts_d, a.view, a.z, w.genc_p0, w.genc_p4, w.genc_d, a.n_rays, a.n_samples,
+                           a.g_pts_o, a.g_pts_d, a.g_view, stream);
+}

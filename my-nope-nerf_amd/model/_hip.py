@@ -64,6 +64,14 @@ class FieldBwd(ctypes.Structure):
                 ("g_view", _c_p), ("workspace", _c_p)]
 
 
+class FieldBwdRays(ctypes.Structure):
+    """nerf_field_bwd_rays (include/nerf_hip.h): the frozen-field backward's arguments."""
+    _fields_ = [("n_pad", _c_i), ("n_rays", _c_i), ("n_samples", _c_i), ("flags", _c_i), ("z", _c_p), ("raw4", _c_p),
+                ("mask", _P10), ("pts_o", _c_p), ("pts_d", _c_p), ("view", _c_p), ("wt", _P10), ("wt_img", _P10),
+                ("wt_cimg", _P10), ("wd", _c_p), ("wc", _c_p), ("g_rgb", _c_p), ("g_dist", _c_p), ("graw4", _c_p),
+                ("g_pts_o", _c_p), ("g_pts_d", _c_p), ("g_view", _c_p), ("workspace", _c_p)]
+
+
 class WgradJob(ctypes.Structure):
     """nerf_wgrad_job (include/nerf_hip.h): one 256 x 256 layer of nerf_linear_bwd_weight_multi."""
     _fields_ = [("dy", _c_p), ("lddy", _c_i), ("x", _c_p), ("ldx", _c_i), ("slab", _c_p), ("ldslab", _c_i),
@@ -113,6 +121,9 @@ _SIGS = {
     "nerf_field_bwd_workspace_bytes": ([_c_i, _c_i], ctypes.c_size_t),
     "nerf_field_backward": ([_c_p, _c_p, _c_p], _c_i),
     "nerf_mlp_chain_bwd": ([_c_p, _c_p], _c_i),
+    "nerf_mlp_chain_bwd_rays": ([_c_p, _c_p], _c_i),
+    "nerf_field_bwd_rays_workspace_bytes": ([_c_i], ctypes.c_size_t),
+    "nerf_field_backward_rays": ([_c_p, _c_p], _c_i),
     "nerf_slab_reduce": ([_c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_i, _c_p], _c_i),
     "nerf_heads_fwd": ([_c_p, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p], _c_i),
     "nerf_heads_part_size": ([_c_i, _c_i], _c_i),
@@ -129,6 +140,8 @@ _SIGS = {
     "nerf_chain_stamps_built": ([], _c_i),
     "nerf_mlp_chain_train": ([_c_p, _c_p, _c_p, _c_p, _c_i, ctypes.POINTER(ChainLayer), _c_p, _c_p, _c_p, _c_p, _c_p,
                               _c_p], _c_i),
+    "nerf_mlp_chain_frozen": ([_c_p, _c_p, _c_p, _c_p, _c_i, ctypes.POINTER(ChainLayer), _c_p, _c_p, _c_p, _c_p, _c_p,
+                               _c_p], _c_i),
     "nerf_render_eval_fused": ([_c_p, _c_p, _c_p, _c_i, _c_i, _c_f, _c_f, _c_i, ctypes.POINTER(ChainLayer), _c_p, _c_p,
                                 _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_adam_step": ([_c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p], _c_i),
@@ -363,6 +376,21 @@ def mlp_chain_bwd(args: ChainBwd):
     _call("nerf_mlp_chain_bwd", ctypes.addressof(args), _stream())
 
 
+def mlp_chain_bwd_rays(args: ChainBwd):
+    """The input-gradient chain storing only D_0, D_5, D_9 and their row maxima (nerf_mlp_chain_bwd_rays)."""
+    _call("nerf_mlp_chain_bwd_rays", ctypes.addressof(args), _stream())
+
+
+def field_bwd_rays_workspace_bytes(n_pad) -> int:
+    return int(lib().nerf_field_bwd_rays_workspace_bytes(n_pad))
+
+
+def field_backward_rays(args: FieldBwdRays):
+    """The ray-gradient-only backward of a frozen D = 256 field in one call (nerf_field_backward_rays),
+    all on the current stream."""
+    _call("nerf_field_backward_rays", ctypes.addressof(args), _stream())
+
+
 def heads_fwd(h8, hr, hidden, wd, bd, wc, bc, raw4, n_pad):
     _call("nerf_heads_fwd", _ptr(h8), _ld(h8), _ptr(hr), _ld(hr), hidden, _ptr(wd), _ptr(bd), _ptr(wc),
           _ptr(bc), _ptr(raw4), n_pad, _stream())
@@ -442,6 +470,17 @@ def mlp_chain_train(enc_p, enc_d, enc_p_rmax, enc_d_rmax, n_pad, layers: Sequenc
         raise ValueError("mlp_chain_train: needs the 10 layer descriptors")
     arr = (ChainLayer * 10)(*layers)
     _call("nerf_mlp_chain_train", _ptr(enc_p), _ptr(enc_d), _ptr(enc_p_rmax), _ptr(enc_d_rmax), int(n_pad), arr,
+          _ptr(wd), _ptr(bd), _ptr(wc), _ptr(bc), _ptr(raw4), _stream())
+
+
+def mlp_chain_frozen(enc_p, enc_d, enc_p_rmax, enc_d_rmax, n_pad, layers: Sequence[ChainLayer], wd, bd, wc, bc,
+                     raw4):
+    """The frozen-field forward chain: mlp_chain_train's launch writing only the ReLU words and
+    raw4 (every descriptor's out and cmax None)."""
+    if len(layers) != 10:
+        raise ValueError("mlp_chain_frozen: needs the 10 layer descriptors")
+    arr = (ChainLayer * 10)(*layers)
+    _call("nerf_mlp_chain_frozen", _ptr(enc_p), _ptr(enc_d), _ptr(enc_p_rmax), _ptr(enc_d_rmax), int(n_pad), arr,
           _ptr(wd), _ptr(bd), _ptr(wc), _ptr(bc), _ptr(raw4), _stream())
 
 

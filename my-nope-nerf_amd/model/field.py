@@ -258,6 +258,69 @@ class FieldRunner:
                          masks=masks, pts_o=pts_o, pts_d=pts_d, view=view, cmaxes=cmaxes)
         return rgb, dist, alpha, z[:N].view(R, S), state
 
+    # ------------------------------------------------------------------ frozen field
+    def forward_rays(self, pts_o, pts_d, view, noise, near, far, S: int, flags: int):
+        """forward() for a render whose backward reaches only the rays (a frozen field: the
+        pose-only step of eval_pose_one_epoch.py:30-76).  In the chain configuration
+        nerf_mlp_chain_frozen runs -- the training chain without its saves -- and the state
+        holds z, raw4, the ReLU words, the ray inputs and the shape fields: no [Np, D] activation
+        and no column-maximum buffer is allocated, and nothing depends on the batch size.  Every
+        other configuration runs forward(keep=True) (backward_rays then skips the weight
+        gradients).  Returns rgb, dist, alpha, z and the state for backward_rays()."""
+        if not self.use_chain(True):
+            rgb, dist, alpha, z, st = self.forward(pts_o, pts_d, view, noise, near, far, S, flags, keep=True)
+            st["frozen"] = False
+            return rgb, dist, alpha, z, st
+        R = pts_o.shape[0]
+        N = R * S
+        Np = _pad_rows(N)
+        dev = pts_o.device
+        e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+        self.pack()
+        z, enc_p, enc_d = e(Np), e(Np, _hip.ENC_P), e(Np, _hip.ENC_D)
+        enc_p_rm, enc_d_rm = e(Np), e(Np)
+        _hip.encode_samples(pts_o, pts_d, view, noise, R, S, Np, near, far, z, enc_p, enc_d,
+                            enc_p_rmax=enc_p_rm, enc_d_rmax=enc_d_rm)
+        masks, descs = {}, []
+        for l in self.layers:
+            mo = None
+            if l.relu:
+                mo = masks[l.name] = torch.empty(Np, l.out_p // 32, device=dev, dtype=torch.int32)
+            ws = self.wsc[l.name]
+            descs.append(_hip.ChainLayer(ws.data_ptr(), ws.shape[2], self.bias(l).data_ptr(), None, l.out_p,
+                                         mo.data_ptr() if mo is not None else None, l.out_p // 32, None))
+        raw4 = e(Np, 4)
+        m = self.m
+        _hip.mlp_chain_frozen(enc_p, enc_d, enc_p_rm, enc_d_rm, Np, descs, m.fc_density.weight, m.fc_density.bias,
+                              self.wc, m.fc_rgb.bias, raw4)
+        rgb, dist, alpha = e(R, 3), e(R), e(R, S)
+        _hip.composite_fwd(raw4, z, R, S, flags, rgb, dist, alpha)
+        state = dict(R=R, S=S, Np=Np, flags=flags, z=z, raw4=raw4, masks=masks, pts_o=pts_o, pts_d=pts_d, view=view,
+                     frozen=True)
+        return rgb, dist, alpha, z[:N].view(R, S), state
+
+    def backward_rays(self, st, g_rgb, g_dist):
+        """-> (g_pts_o, g_pts_d, g_view) [R, 3] of a forward_rays() state: nerf_field_backward_rays
+        (composite backward, the ray-gradient chain, three 64-wide input-gradient GEMMs, the
+        encoding backward, on the current stream) or, outside the chain configuration, the
+        Python schedule without its weight gradients."""
+        if not st["frozen"]:
+            return self.backward(st, g_rgb, g_dist, True, want_weight_grad=False)[1]
+        Np, R, S = st["Np"], st["R"], st["S"]
+        dev = st["z"].device
+        names = [l.name for l in self.layers]
+        P = lambda t: None if t is None else t.data_ptr()            # noqa: E731
+        ray = tuple(torch.empty(R, 3, device=dev) for _ in range(3))
+        ws = torch.empty(_hip.field_bwd_rays_workspace_bytes(Np), device=dev, dtype=torch.uint8)
+        args = _hip.FieldBwdRays(
+            Np, R, S, st["flags"], P(st["z"]), P(st["raw4"]), _hip._P10(*[P(st["masks"].get(n)) for n in names]),
+            P(st["pts_o"]), P(st["pts_d"]), P(st["view"]), _hip._P10(*[self.wt[n].data_ptr() for n in names]),
+            _hip._P10(*[self.wts[n].data_ptr() for n in names]), _hip._P10(*[self.wtsc[n].data_ptr() for n in names]),
+            self.wd.data_ptr(), self.wc.data_ptr(), P(g_rgb), P(g_dist), None, *[t.data_ptr() for t in ray],
+            ws.data_ptr())
+        _hip.field_backward_rays(args)
+        return ray
+
     def use_chain(self, keep: bool = False) -> bool:
         """The fused layer chain (chain.hip) covers precision mode 2 at hidden 256 / colour
         128, and is the default there.  Eval renders (keep=False) run nerf_mlp_chain_fwd (or
@@ -378,12 +441,15 @@ class FieldRunner:
             pl = self._plist = list(self.m.parameters())
         return pl
 
-    def backward(self, st, g_rgb, g_dist, want_ray_grad: bool, graw4=None, g_h8=None):
+    def backward(self, st, g_rgb, g_dist, want_ray_grad: bool, graw4=None, g_h8=None, want_weight_grad: bool = True):
         """Returns (list of parameter gradients in self.param_list() order, ray grads or None).
         Starts from the ray gradients (composite backward) or, when ``graw4`` is given,
         directly from the gradient of the raw head outputs.  ``g_h8`` [Np, D] (optional): an
         extra gradient w.r.t. the trunk output h8 (infer_occ's x), added where l7's ReLU
-        passes it."""
+        passes it.  ``want_weight_grad=False`` (a frozen field: backward_rays outside the chain
+        configuration) runs the input-gradient launches of the Python schedule alone -- no
+        gradient buffer, head-weight partial, weight gradient or side stream -- and returns
+        None for the parameter gradients."""
         R, S, Np, flags = st["R"], st["S"], st["Np"], st["flags"]
         D, HR = self.D, self.HR
         dev = st["z"].device
@@ -391,10 +457,12 @@ class FieldRunner:
         acts = st["acts"]
         h = {l.name: acts[i] for i, l in enumerate(self.layers)}
         m = self.m
-        params = self.param_list()
+        params = self.param_list() if want_weight_grad else []
         n_par = sum(p.numel() for p in params)
         buf = self.grad_buffer
-        if (buf is not None and not self.grad_buffer_taken and buf.device == dev and buf.numel() >= n_par
+        if not want_weight_grad:
+            flat = None
+        elif (buf is not None and not self.grad_buffer_taken and buf.device == dev and buf.numel() >= n_par
                 and all(p.grad is None for p in params)):
             # autograd hands these views on as param.grad (no other gradient to accumulate into)
             flat = buf[:n_par]
@@ -407,7 +475,7 @@ class FieldRunner:
             off += p.numel()
         G = lambda p: grads[id(p)]
 
-        if g_h8 is None and self.native_backward(Np):
+        if g_h8 is None and want_weight_grad and self.native_backward(Np):
             return [G(p) for p in params], self._backward_native(st, g_rgb, g_dist, want_ray_grad, graw4, G)
         if graw4 is None:
             graw4 = e(Np, 4)
@@ -426,10 +494,10 @@ class FieldRunner:
         # re-read h8 and hr) and their reduce run on the side stream, beside dyr and the colour
         # layer's input gradient, before that stream's first weight gradient needs dyr
         dyr = e(Np, HR)
-        rm, cm = self._rmax_alloc(Np, dev), self._cmax_alloc(Np, dev)
+        rm, cm = self._rmax_alloc(Np, dev), self._cmax_alloc(Np, dev, want_weight_grad)
         dy_rm, dy_cm = rm(HR), cm(HR)
         split_heads = self.heads_side(Np)
-        gw = (G(m.fc_density.weight), G(m.fc_density.bias), G(m.fc_rgb.bias))
+        gw = (G(m.fc_density.weight), G(m.fc_density.bias), G(m.fc_rgb.bias)) if want_weight_grad else None
 
         def head_weights(mode):
             part = e(_hip.heads_part_size(D, Np))
@@ -440,7 +508,11 @@ class FieldRunner:
             if HR != D // 2:
                 G(m.fc_rgb.weight).copy_(gwc[:, :D // 2])
 
-        if split_heads:
+        if not want_weight_grad:     # dyr alone (mode 1), gated by the ReLU words when the forward kept them
+            lr_mask = st["masks"].get("lr")
+            _hip.heads_bwd(graw4, None, h["lr"] if lr_mask is None else None, D, self.wc, dyr, None, Np,
+                           dyr_rmax=dy_rm, dyr_cmax=dy_cm, mode=1, hr_mask=lr_mask)
+        elif split_heads:
             ev = torch.cuda.Event()
             ev.record(main)
             sides[0].wait_event(ev)
@@ -513,7 +585,9 @@ class FieldRunner:
             # --- weight / bias gradient on a side stream: split-K slabs + reduce.  The last
             # NERF_TAIL_MAIN layers' run on the main stream once the input-gradient chain is done
             # (every cross-stream wait costs ~15 us before the next launch)
-            if step >= len(order) - tail_main:
+            if not want_weight_grad:
+                pass
+            elif step >= len(order) - tail_main:
                 deferred.append((l, dy, dy_cm, x_in))
             else:
                 side = sides[0]
@@ -564,7 +638,7 @@ class FieldRunner:
 
         for args in deferred:
             weight_grad(*args)
-        for side in sides:
+        for side in (sides if want_weight_grad else []):
             done = torch.cuda.Event()
             done.record(side)
             main.wait_event(done)           # gradients complete before autograd hands them on
@@ -574,7 +648,7 @@ class FieldRunner:
             _hip.encode_bwd(st["pts_o"], st["pts_d"], st["view"], st["z"], genc["p0"], genc["d"], R, S,
                             g_po, g_pd, g_view, genc_p2=genc["p4"])
             ray = (g_po, g_pd, g_view)
-        return [G(p) for p in params], ray
+        return ([G(p) for p in params] if want_weight_grad else None), ray
 
 
 class FieldRenderFn(torch.autograd.Function):
@@ -610,10 +684,45 @@ class FieldRenderFn(torch.autograd.Function):
         return (None, g_po, g_pd, g_view, None, None, None, None, None, *grads)
 
 
-def render_field(module, pts_o, pts_d, view, noise, near, far, S, flags):
-    """Differentiable render of R rays through the HIP path (training)."""
+class FieldRaysFn(torch.autograd.Function):
+    """FieldRenderFn for a frozen field: the inputs are the ray tensors alone, so no field
+    parameter is an autograd input and none receives a ``.grad`` (FieldRunner.forward_rays /
+    backward_rays)."""
+
+    @staticmethod
+    def forward(ctx, runner: FieldRunner, pts_o, pts_d, view, noise, near, far, S, flags):
+        ctx.set_materialize_grads(False)
+        rgb, dist, alpha, z, st = runner.forward_rays(pts_o, pts_d, view, noise, near, far, S, flags)
+        ctx.runner = runner
+        ctx.state = st
+        ctx.mark_non_differentiable(alpha, z)
+        return rgb, dist, alpha, z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_rgb, g_dist, g_alpha, g_z):
+        st = ctx.state
+        R = st["R"]
+        if g_rgb is None:
+            g_rgb = torch.zeros(R, 3, device=st["z"].device)
+        if g_dist is None:
+            g_dist = torch.zeros(R, device=st["z"].device)
+        g_po, g_pd, g_view = ctx.runner.backward_rays(st, g_rgb.contiguous(), g_dist.contiguous())
+        ctx.state = None
+        return (None, g_po, g_pd, g_view, None, None, None, None, None)
+
+
+def render_field(module, pts_o, pts_d, view, noise, near, far, S, flags, field_grad=True):
+    """Differentiable render of R rays through the HIP path (training).  ``field_grad=False``,
+    or a field none of whose parameters requires a gradient, takes the frozen path
+    (FieldRaysFn): the gradients reach the rays only, and the weight gradients -- which
+    autograd would discard -- are never computed."""
     runner = module.hip_runner()
     params = runner.param_list()
+    if not field_grad or not any(p.requires_grad for p in params):
+        return FieldRaysFn.apply(runner, pts_o.contiguous(), pts_d.contiguous(), view.contiguous(),
+                                 None if noise is None else noise.contiguous(), float(near), float(far),
+                                 int(S), int(flags))
     return FieldRenderFn.apply(runner, pts_o.contiguous(), pts_d.contiguous(), view.contiguous(),
                                None if noise is None else noise.contiguous(), float(near), float(far),
                                int(S), int(flags), *params)

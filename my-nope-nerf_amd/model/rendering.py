@@ -196,12 +196,14 @@ class Renderer(nn.Module):
         return torch.norm(normals[:n] - normals[n:], dim=-1)
 
     def nope_nerf(self, pixels, depth, camera_mat, world_mat, scale_mat, add_noise=False, it=100000,
-                  eval_=False, noise=None, dense_depth=False, normal_noise=None):
+                  eval_=False, noise=None, dense_depth=False, normal_noise=None, field_grad=True):
         """rendering.py:36-168.  Extra keyword arguments of the MI355X build:
         ``noise`` injects the stratified U[0,1) tensor (1,R,S) instead of torch.rand;
         ``dense_depth`` returns unmasked depth_pred/depth_gt plus 'depth_mask' (R,) so the
         training step never needs the boolean-index host sync (rendering.py:151-153);
-        ``normal_noise`` injects the (N,3) jitter of the normal_loss branch."""
+        ``normal_noise`` injects the (N,3) jitter of the normal_loss branch;
+        ``field_grad=False`` renders a frozen field: gradients reach the camera matrices only
+        and no field parameter gets a ``.grad`` (Trainer_pose, eval_pose_one_epoch.py:44-61)."""
         cfg = self.cfg
         S = cfg["num_points"] - cfg.get("outside_steps", 0)
         near, far = float(self.depth_range[0]), float(self.depth_range[1])
@@ -227,7 +229,8 @@ class Renderer(nn.Module):
                 nz = nz.reshape(R, S).float()
         flags = self._flags()
         if torch.is_grad_enabled():
-            rgb, dist, alpha, z = render_field(self.model, pts_o, pts_d, view, nz, near_s, far_s, S, flags)
+            rgb, dist, alpha, z = render_field(self.model, pts_o, pts_d, view, nz, near_s, far_s, S, flags,
+                                               field_grad=field_grad)
         else:
             rgb, dist, alpha, z = render_field_eval(self.model, pts_o, pts_d, view, near_s, far_s, S, flags) \
                 if nz is None else render_field(self.model, pts_o, pts_d, view, nz, near_s, far_s, S, flags)
