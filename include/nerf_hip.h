@@ -509,7 +509,8 @@ int nerf_encode_bwd(const float* pts_o, const float* pts_d, const float* view, c
  * 16x16x32 MFMA accumulators of the two-wave chains hold a layer's outputs.  perm_k % 32 == 0,
  * ld_t % 32 == 0 when dst_cts is given.  Since ABI 15 the chain images also hold every row's
  * exponent in a compact int32 array at plane 2's chunk 1 (u16 index (2*K/8 + 1)*rows*8 + 2 r),
- * which the chain kernels load with one 1 KB LDS-DMA per layer. */
+ * which the chain kernels load with one 1 KB LDS-DMA per layer; an image of a single chunk has
+ * no chunk 1, so dst_cs needs ld_dst >= 16 and dst_cts ld_t >= 16 (NERF_EINVAL otherwise). */
 #define NERF_MAX_PACK 24
 typedef struct {
     const float* src;

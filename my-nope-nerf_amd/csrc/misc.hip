@@ -260,6 +260,11 @@ extern "C" int nerf_pack_weights(const nerf_pack_desc* descs, int n, void* strea
         NERF_CHECK(d.dst_ts == nullptr || (d.rows_t >= d.cols && d.ld_t >= d.rows && d.ld_t % 8 == 0),
                    "%s: descriptor %d: transposed split image needs rows_t >= cols, ld_t >= rows, ld_t %% 8 == 0",
                    __func__, i);
+        // the compact exponent array sits at plane 2's chunk 1: an image of one chunk (K = 8) has none
+        NERF_CHECK(d.dst_cs == nullptr || d.ld_dst >= 16, "%s: descriptor %d: the chain image needs ld_dst >= 16",
+                   __func__, i);
+        NERF_CHECK(d.dst_cts == nullptr || d.ld_t >= 16, "%s: descriptor %d: the transposed chain image needs ld_t >= 16",
+                   __func__, i);
         NERF_CHECK((d.dst_cs == nullptr && d.dst_cts == nullptr) ||
                        (pb.f16 && d.perm_k >= 0 && d.perm_k % 32 == 0 && d.perm_k <= d.ld_dst && d.ld_dst % 8 == 0 &&
                         d.ld_dst <= PACK_H_MAXK),

@@ -765,3 +765,17 @@ def test_bad_arguments_raise(dev):
         _hip.linear_fwd(x, 256, None, 0, W, None, y, 100, 256, 1)
     with pytest.raises(RuntimeError, match="GPU"):
         _hip.linear_fwd(x.cpu(), 256, None, 0, W, None, y, 128, 256, 1)
+    # nerf_pack_weights: a chain image of one 8-column chunk has no plane-2 chunk 1 for the compact
+    # exponent array (it would be written past the image's end): refused on the host, nothing launches
+    _hip.gemm_set_precision(2)
+    src = torch.ones(8, 8, device=dev)
+    dst, dst_t = torch.zeros(8, 8, device=dev), torch.zeros(8, 8, device=dev)
+    guard = torch.full((3 * 8 * 8 + 64,), 0x5a5a, dtype=torch.int16, device=dev)      # an 8 x 8 image + a tail
+    with pytest.raises(RuntimeError, match="chain image needs ld_dst >= 16"):
+        _hip.pack_weights([_hip.PackDesc(src.data_ptr(), dst.data_ptr(), None, 8, 8, 8, 0, 0, None, None, 8,
+                                         guard.data_ptr(), None, 0)])
+    with pytest.raises(RuntimeError, match="transposed chain image needs ld_t >= 16"):
+        _hip.pack_weights([_hip.PackDesc(src.data_ptr(), dst.data_ptr(), dst_t.data_ptr(), 8, 8, 8, 8, 8, None, None, 8,
+                                         None, guard.data_ptr(), 0)])
+    torch.cuda.synchronize()
+    assert bool((guard == 0x5a5a).all()) and bool((dst == 0).all())

@@ -13,6 +13,7 @@ from model import _hip
 from model.common import arange_pixels
 from oracle import nerf_oracle as orc
 from tests.helpers import assert_elementwise, camera_K, make_cfg, rigid_c2w, synthetic_rays
+from tests.helpers import chain_bwd_args as _chain_bwd_args, chain_descs as _chain_descs, chain_kernel_state as _kernel_state
 
 pytestmark = pytest.mark.gpu
 
@@ -34,44 +35,6 @@ def _nrel(a, b):
 
 
 # ------------------------------------------------------------------ kernel level
-def _chain_descs(runner, outs, masks, cmaxes):
-    descs = []
-    for i, l in enumerate(runner.layers):
-        ws = runner.wsc[l.name]
-        P = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        descs.append(_hip.ChainLayer(ws.data_ptr(), ws.shape[2], runner.bias(l).data_ptr(), P(outs[i]), l.out_p,
-                                     P(masks[i]), l.out_p // 32, P(cmaxes[i])))
-    return descs
-
-
-def _kernel_state(dev):
-    """Seeded D = 256 field, encodings of 12 rays x 32 samples, and nerf_mlp_chain_train's saves."""
-    torch.manual_seed(7)
-    net = mdl.OfficialStaticNerf(make_cfg(hidden=256, S=S0)).to(dev)
-    runner = net.hip_runner()
-    runner.pack()
-    g = torch.Generator().manual_seed(8)
-    o = ((torch.rand(R0, 3, generator=g) - 0.5) * 4).to(dev)
-    d = F.normalize(torch.rand(R0, 3, generator=g) - 0.5, dim=-1).to(dev)
-    view = (-d).contiguous()
-    e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)      # noqa: E731
-    z, enc_p, enc_d, rp, rd = e(NP), e(NP, 64), e(NP, 64), e(NP), e(NP)
-    cp, cd = e(NP // 128, 64), e(NP // 128, 64)
-    _hip.encode_samples(o, d, view, None, R0, S0, NP, 0.01, 10.0, z, enc_p, enc_d, enc_p_rmax=rp, enc_d_rmax=rd,
-                        enc_p_cmax=cp, enc_d_cmax=cd)
-    m = net
-    heads = (m.fc_density.weight, m.fc_density.bias, runner.wc, m.fc_rgb.bias)
-    new_masks = lambda: [torch.zeros(NP, l.out_p // 32, device=dev, dtype=torch.int32) if l.relu else None    # noqa: E731
-                         for l in runner.layers]
-    outs = [e(NP, l.out_p) for l in runner.layers]
-    cmaxes = [e(NP // 128, l.out_p) if l.name != "lr" else None for l in runner.layers]
-    masks, raw4 = new_masks(), e(NP, 4)
-    _hip.mlp_chain_train(enc_p, enc_d, rp, rd, NP, _chain_descs(runner, outs, masks, cmaxes), *heads, raw4)
-    torch.cuda.synchronize()
-    return dict(net=net, runner=runner, o=o, d=d, view=view, z=z, enc_p=enc_p, enc_d=enc_d, rp=rp, rd=rd, cp=cp, cd=cd,
-                heads=heads, outs=outs, cmaxes=cmaxes, masks=masks, raw4=raw4, new_masks=new_masks)
-
-
 def test_chain_frozen_bit_identical_to_chain_train(dev, h16):
     """The same arithmetic without the saves: every ReLU word and raw4 equal nerf_mlp_chain_train's
     bit for bit, and the buffers the training chain wrote (out, cmax) stay untouched."""
@@ -97,28 +60,6 @@ def test_chain_frozen_bit_identical_to_chain_train(dev, h16):
     with pytest.raises(RuntimeError, match="out and cmax"):
         _hip.mlp_chain_frozen(k["enc_p"], k["enc_d"], k["rp"], k["rd"], NP,
                               _chain_descs(runner, [guards[0]] + [None] * 9, masks2, none), *k["heads"], raw4_2)
-
-
-def _chain_bwd_args(k, graw4, dy, cm, rm, scratch):
-    runner = k["runner"]
-    names = [l.name for l in runner.layers]
-    c = _hip.ChainBwd()
-    c.graw4, c.hr_mask, c.ld_hr_mask = graw4.data_ptr(), k["masks"][9].data_ptr(), 4
-    c.wd, c.wc = runner.wd.data_ptr(), runner.wc.data_ptr()
-    for i in range(9):
-        l = 9 - i
-        c.wt_img[i] = runner.wtsc[names[l]].data_ptr()
-        c.wt_img_rows[i] = runner.layers[l].kp
-        c.in_mask[i] = None if i == 0 else k["masks"][l - 1].data_ptr()
-        c.ld_in_mask[i] = 8
-    for i in range(10):
-        c.dy[i] = None if dy[i] is None else dy[i].data_ptr()
-        c.lddy[i] = 128 if i == 0 else 256
-        c.dy_cmax[i] = None if cm[i] is None else cm[i].data_ptr()
-        c.dy_rmax[i] = None if rm[i] is None else rm[i].data_ptr()
-    c.scratch = None if scratch is None else scratch.data_ptr()
-    c.n_pad = NP
-    return c
 
 
 def test_chain_bwd_rays_bit_identical_to_chain_bwd(dev, h16):

@@ -139,6 +139,73 @@ def test_render_backward_as_accurate_as_reference(dev, gemm_precision):
         assert e_hip <= 1.5 * e_ref + 1e-5, f"{n}: HIP {e_hip:.2e} vs the fp32 reference's {e_ref:.2e} (both vs fp64)"
 
 
+def test_padded_chain_render_and_gradients_match_oracle(dev):
+    """The production schedule (the forward and backward chains, the native backward with the split
+    heads) on a batch that does not fill its last 128-row block: D = 256, 29 rays x 50 samples, so
+    n_pad = 1536 with 86 padded rows, which the weight gradients sum over.  rgb and dist elementwise
+    against the oracle; every parameter gradient, g_pts_o and g_pts_d within 1.5x (+1e-5) of the fp32
+    oracle's own distance from fp64 (the bar of test_render_backward_as_accurate_as_reference)."""
+    import os
+    from model import _hip
+    from model.field import render_field
+    R, S = 29, 50
+    cfg = make_cfg(hidden=256, S=S)
+    net, ref = _pair(cfg, 5)
+    net = net.to(dev)
+    g = torch.Generator().manual_seed(13)
+    o = (torch.rand(R, 3, generator=g) - 0.5) * 4
+    d = torch.nn.functional.normalize(torch.rand(R, 3, generator=g) - 0.5, dim=-1)
+    noise = torch.rand(R, S, generator=g)
+    w_rgb = torch.randn(R, 3, generator=g)
+    _hip.gemm_set_precision(2)
+    env = {"NERF_CHAIN": "1", "NERF_BWD_CHAIN": "1", "NERF_HEADS_SIDE": "1"}
+    old = {n: os.environ.get(n) for n in env}
+    os.environ.update(env)
+    try:
+        runner = net.hip_runner()
+        runner.pack()
+        assert runner.use_chain(True) and runner.native_backward(1536) and runner.bwd_chain()
+        od, dd = o.to(dev).requires_grad_(True), d.to(dev).requires_grad_(True)
+        rgb, dist, alpha, z = render_field(net, od, dd, (-d).to(dev), noise.to(dev), 0.01, 10.0, S, 0)
+        ((rgb * w_rgb.to(dev)).sum() + 0.1 * dist.sum()).backward()
+        torch.cuda.synchronize()
+    finally:
+        for n, v in old.items():
+            if v is None:
+                os.environ.pop(n, None)
+            else:
+                os.environ[n] = v
+    zc = z.detach().cpu()
+
+    def oracle(dtype):
+        r = orc.OracleNerf(hidden_dim=256).to(dtype)
+        r.load_state_dict({k: v.to(dtype) for k, v in ref.state_dict().items()})
+        oo, do = o.clone().to(dtype).requires_grad_(True), d.clone().to(dtype).requires_grad_(True)
+        zz = zc.to(dtype)
+        pts = oo[:, None, :] + do[:, None, :] * zz[..., None]
+        view = (-d).to(dtype)[:, None, :].expand(R, S, 3)
+        rgb_s, a_s = r(pts.reshape(-1, 3), view.reshape(-1, 3))
+        ro = orc.composite(a_s.reshape(R, S), rgb_s.reshape(R, S, 3), zz)
+        ((ro[0] * w_rgb.to(dtype)).sum() + 0.1 * ro[1].sum()).backward()
+        grads = {n: p.grad.double() for n, p in r.named_parameters()}
+        grads.update(g_pts_o=oo.grad.double(), g_pts_d=do.grad.double())
+        return ro[0].detach(), ro[1].detach(), grads
+    rgb32, dist32, g32 = oracle(torch.float32)
+    _, _, g64 = oracle(torch.float64)
+    assert_elementwise(rgb, rgb32, what="rgb")
+    assert_elementwise(dist, dist32, what="dist")
+    got = {n: p.grad for n, p in net.named_parameters()}
+    got.update(g_pts_o=od.grad, g_pts_d=dd.grad)
+    assert set(got) == set(g64)
+    for n, gh in got.items():
+        e_hip = ((gh.double().cpu() - g64[n]).norm() / g64[n].norm()).item()
+        e_ref = ((g32[n] - g64[n]).norm() / g64[n].norm()).item()
+        report_err("padded_vs_fp64_hip", n, e_hip)
+        report_err("padded_vs_fp64_ref32", n, e_ref)
+        print(f"{n}: HIP {e_hip:.3e}, fp32 oracle {e_ref:.3e} (both vs fp64)")
+        assert e_hip <= 1.5 * e_ref + 1e-5, f"{n}: HIP {e_hip:.2e} vs the fp32 reference's {e_ref:.2e} (both vs fp64)"
+
+
 def test_render_ray_gradients(dev, gemm_precision):
     """pose learning: gradients w.r.t. the camera pose flow through the encodings."""
     cfg = make_cfg(hidden=64, S=64)
