@@ -43,7 +43,8 @@ extern "C" {
  * Adam hyper slot 6 (1 - beta2), 13 the chain images (nerf_pack_desc dst_cs / dst_cts, nerf_field_bwd
  * wt_cimg) and torch-exact Adam, 14 nerf_linear_bwd_weight_jobs and nerf_pair_backward's 12P gXY,
  * 15 the chain images' compact exponent arrays (nerf_pack_desc dst_cs / dst_cts) and
- * nerf_linear_bwd_weight_job_groups. */
+ * nerf_linear_bwd_weight_job_groups.  Additive within 15 (no existing signature changed): the
+ * frozen-field entries and nerf_image_metrics(_workspace_bytes). */
 #define NERF_HIP_ABI_VERSION 15
 int nerf_hip_abi_version(void);
 const char* nerf_hip_last_error(void);
@@ -663,6 +664,26 @@ int nerf_pair_backward(const float* d1, const float* d2, int h, int w, const flo
                        const float* work, const int* nn, const float* out3, const float* go_pc,
                        const float* go_rgbs, float* gXY, float* g_d1, float* g_d2, float* g13, float* part13,
                        void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Windowed image metrics of the novel-view evaluation (metrics.hip; model/eval_images.py:94-97:
+ * F.mse_loss and third_party/pytorch_ssim/__init__.py:8-46).  Per image b of the batch,
+ *   out[b] = { mean (img1 - img2)^2 over channel, row, column,
+ *              mean of the SSIM map over channel, row, column (size_average=False, :46) },
+ * the map being :27-41 with the `window`-tap Gaussian of sigma 1.5 (:8-17; window odd, 1..11),
+ * zero padding of window / 2 when use_padding, else a valid convolution of
+ * (height - window + 1) x (width - window + 1) outputs; C1 = 0.01^2, C2 = 0.03^2.
+ * Both images are addressed by four element strides (batch, channel, row, column), so a
+ * renderer's [H][W][3] frame and a loader's [1][3][H][W] image, or any slice of either, are
+ * read in place.  ssim_map (optional): contiguous [batch][channels][out rows][out columns].
+ * workspace: nerf_image_metrics_workspace_bytes bytes, 8-byte aligned (one pair of partial sums
+ * per 32 x 32 tile, summed in a fixed order: no atomics, repeatable bits).  Two launches; the
+ * filters and the map are evaluated in fp64 and rounded to f32 once. */
+size_t nerf_image_metrics_workspace_bytes(int batch, int channels, int height, int width);
+int nerf_image_metrics(const float* img1, int64_t s1_batch, int64_t s1_channel, int64_t s1_row, int64_t s1_col,
+                       const float* img2, int64_t s2_batch, int64_t s2_channel, int64_t s2_row, int64_t s2_col,
+                       int batch, int channels, int height, int width, int window, int use_padding, float* out,
+                       float* ssim_map, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Timing hooks for bench.py: when enabled, every GEMM launch is bracketed by

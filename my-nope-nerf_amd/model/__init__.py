@@ -5,9 +5,10 @@ names the reference's train.py and vis/render.py use (mdl.OfficialStaticNerf,
 mdl.Renderer, mdl.get_model, mdl.LearnPose, mdl.Learn_Distortion, mdl.LearnFocal,
 mdl.Trainer, mdl.CheckpointIO) and evaluation/eval.py's test-time pose refinement
 (mdl.Trainer_pose), backed by the nerf_hip kernels; the submodules ``model.common``,
-``model.extracting_images`` and ``model.eval_pose_one_epoch`` carry the names those drivers
-import (tests/test_dropin_names.py, tests/test_pose_refine_names.py).  Out of scope
-(SURVEY.md section 2): DPT.
+``model.extracting_images``, ``model.eval_pose_one_epoch`` and ``model.eval_images`` (Eval_Images,
+evaluation/eval.py:14; like the reference's package, not re-exported here) carry the names those
+drivers import (tests/test_dropin_names.py, tests/test_pose_refine_names.py,
+tests/test_eval_images_cpu.py).  Out of scope: DPT.
 """
 from .checkpoints import CheckpointIO
 from .config import get_model

@@ -172,6 +172,9 @@ _SIGS = {
     "nerf_pair_forward": ([_c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_pair_backward": ([_c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p,
                             _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_image_metrics_workspace_bytes": ([_c_i, _c_i, _c_i, _c_i], ctypes.c_size_t),
+    "nerf_image_metrics": ([_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i, _c_i,
+                            _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_prof_enable": ([_c_i], _c_i),
     "nerf_prof_read_kinds": ([ctypes.POINTER(ProfKind), _c_i], _c_i),
     "nerf_prof_read": ([ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64),
@@ -585,6 +588,27 @@ def pair_backward(d1, d2, h, w, K, Rt, s1, nl, img1, img2, rgbs_detach_scale, wo
     _call("nerf_pair_backward", _ptr(d1), _ptr(d2), int(h), int(w), _ptr(K), _ptr(Rt), _ptr(s1), float(nl),
           _ptr(img1), _ptr(img2), int(rgbs_detach_scale), _ptr(work), _ptr(nn), _ptr(out3), _ptr(go_pc),
           _ptr(go_rgbs), _ptr(gxy), _ptr(g_d1), _ptr(g_d2), _ptr(g13), _ptr(part13), _stream())
+
+
+def image_metrics_workspace_bytes(batch, channels, height, width) -> int:
+    return int(lib().nerf_image_metrics_workspace_bytes(int(batch), int(channels), int(height), int(width)))
+
+
+def image_metrics(img1, img2, window, use_padding, out, work, ssim_map=None):
+    """out [B][2] = (mse, mean SSIM) of two float32 [B,C,H,W] views of any strides, read in place
+    (nerf_image_metrics); work: image_metrics_workspace_bytes bytes; ssim_map: optional contiguous
+    [B][C][H'][W'] output."""
+    if img1.dim() != 4 or img1.shape != img2.shape:
+        raise ValueError(f"image_metrics: two [B,C,H,W] tensors of one shape expected, got {tuple(img1.shape)} "
+                         f"and {tuple(img2.shape)}")
+    for t in (img1, img2, out, ssim_map):
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError("image_metrics: float32 tensors expected")
+    if not out.is_contiguous() or (ssim_map is not None and not ssim_map.is_contiguous()):
+        raise RuntimeError("image_metrics: contiguous outputs expected")
+    b, c, h, w = img1.shape
+    _call("nerf_image_metrics", _ptr(img1), *img1.stride(), _ptr(img2), *img2.stride(), b, c, h, w, int(window),
+          int(bool(use_padding)), _ptr(out), _ptr(ssim_map), _ptr(work), _stream())
 
 
 def chamfer_nn(x, y, idx):
