@@ -1250,13 +1250,11 @@ extern "C" int nerf_heads_reduce(const float* part, int hidden, int n_pad, float
     return check_launch(__func__);
 }
 
+// the wave-per-ray kernels: reached only above 256 samples (J_ >= 5), the 16-lane family below
 #define NERF_J_DISPATCH(KERNEL, S, ...)                                            \
     do {                                                                           \
         const int J_ = ((S) + 63) / 64;                                            \
-        if (J_ <= 1) hipLaunchKernelGGL((KERNEL<1>), __VA_ARGS__);                 \
-        else if (J_ == 2) hipLaunchKernelGGL((KERNEL<2>), __VA_ARGS__);            \
-        else if (J_ <= 4) hipLaunchKernelGGL((KERNEL<4>), __VA_ARGS__);            \
-        else if (J_ <= 8) hipLaunchKernelGGL((KERNEL<8>), __VA_ARGS__);            \
+        if (J_ <= 8) hipLaunchKernelGGL((KERNEL<8>), __VA_ARGS__);                 \
         else if (J_ <= 16) hipLaunchKernelGGL((KERNEL<16>), __VA_ARGS__);          \
         else NERF_CHECK(false, "%s: n_samples=%d > 1024", __func__, (int)(S));     \
     } while (0)

@@ -354,3 +354,97 @@ def chain_test_rays(R=5, seed=3):
     o = (torch.rand(R, 3, generator=g) - 0.5) * 4
     d = torch.nn.functional.normalize(torch.rand(R, 3, generator=g) - 0.5, dim=-1)
     return o, d
+
+
+# ---- the per-ray kernels (csrc/render.hip, misc.hip): fp64 references and edge inputs ----------
+# Sample counts of tests/test_gpu_ray_kernels_fp64.py: the 16-lanes-per-ray composite family
+# (S <= 256: every J arm, S == 16 J, a partial last lane, both sides of S % 4) and the wave-per-ray
+# family (256 < S <= 1024).
+COMPOSITE_S16 = (1, 2, 15, 16, 17, 31, 32, 33, 34, 36, 63, 64, 65, 100, 127, 128, 129, 132, 255, 256)
+COMPOSITE_SWAVE = (257, 511, 512, 513, 1000, 1023, 1024)
+COMPOSITE_R = 37
+COMPOSITE_KINDS = ("generic", "saturated")
+COMPOSITE_T = dict(rgb=1e-5, dist=1e-4, alpha=1e-5)      # the fixed bars of test_composite_fwd_bwd
+COMPOSITE_T_GRAD = 2e-4                                   # times max(1, max |ref|)
+F32_MARGIN = 4.0                                          # |hip - f64| <= T_project + F32_MARGIN E_f32
+
+
+def composite_ref(raw, z, flags, g_rgb, g_dist, dtype):
+    """The composite and its backward in plain torch at `dtype`: density activation (ReLU or
+    softplus; 1 - exp(-sigma) unless dist_alpha), colour sigmoid, oracle.composite, autograd of
+    sum(rgb g_rgb) + sum(dist g_dist).  raw [R*S][4], z [R][S] -> (rgb [R][3], dist [R],
+    alpha [R][S], graw [R*S][4]).  float64: the reference; float32: the reference's own arithmetic."""
+    from oracle import nerf_oracle as orc
+    R, S = z.shape
+    rr = raw.detach().cpu().to(dtype).clone().requires_grad_(True)
+    zz = z.detach().cpu().to(dtype)
+    sig = torch.relu(rr[:, 0]) if flags & 4 else torch.nn.functional.softplus(rr[:, 0])
+    if not flags & 1:
+        sig = 1 - torch.exp(-sig)
+    c = torch.sigmoid(rr[:, 1:])
+    rgb, dist, alpha, _ = orc.composite(sig.view(R, S), c.view(R, S, 3), zz, dist_alpha=bool(flags & 1),
+                                        white_background=bool(flags & 2))
+    loss = (rgb * g_rgb.detach().cpu().to(dtype)).sum() + (dist * g_dist.detach().cpu().to(dtype)).sum()
+    loss.backward()
+    return rgb.detach(), dist.detach(), alpha.detach(), rr.grad
+
+
+def composite_edge_inputs(R, S, seed, kind):
+    """(raw [R*S][4], z [R][S], g_rgb [R][3], g_dist [R]) in f32.  "generic": the distribution of
+    test_composite_fwd_bwd (randn * 2, density logit + 0.5, depths sorted in [0.01, 9.01]).
+    "saturated": ray r takes pattern r % 6 on top of it -- 0: density logit -30 everywhere (an empty
+    ray); 1: +30 from sample S/3 on (softplus' x > 20 branch, alpha = 1: the transmittance runs
+    through eps^k and underflows in f32); 2: alternating +25 / -25; 3: colour logits +-40; 4: density
+    logit exactly 0 on the first half (the ReLU kink); 5: for S > 2, samples 1 .. S/2 at one repeated
+    depth (dist_alpha's delta = 0).  Rays 7, 19, 31, ... carry a zero upstream gradient."""
+    assert kind in COMPOSITE_KINDS, kind
+    g = torch.Generator().manual_seed(seed)
+    raw = torch.randn(R, S, 4, generator=g) * 2
+    raw[:, :, 0] += 0.5
+    z = torch.sort(torch.rand(R, S, generator=g) * 9 + 0.01, dim=1)[0]
+    g_rgb = torch.randn(R, 3, generator=g)
+    g_dist = torch.randn(R, generator=g) * 0.1
+    g_rgb[7::12] = 0
+    g_dist[7::12] = 0
+    if kind == "saturated":
+        i = torch.arange(S)
+        for r in range(R):
+            p = r % 6
+            if p == 0:
+                raw[r, :, 0] = -30.0
+            elif p == 1:
+                raw[r, S // 3:, 0] = 30.0
+            elif p == 2:
+                raw[r, :, 0] = torch.where(i % 2 == 0, 25.0, -25.0)
+            elif p == 3:
+                raw[r, :, 1:] = torch.where((i[:, None] + torch.arange(3)[None, :]) % 2 == 0, 40.0, -40.0)
+            elif p == 4:
+                raw[r, :(S + 1) // 2, 0] = 0.0
+            elif S > 2:
+                z[r, 1:S // 2 + 1] = z[r, S // 2].clone()
+    return raw.reshape(R * S, 4).contiguous(), z.contiguous(), g_rgb, g_dist
+
+
+def composite_refs(raw, z, flags, g_rgb, g_dist):
+    """(the f64 reference, E_f32): E_f32[name] = max |f32 reference - f64 reference| of rgb, dist,
+    alpha and grad on these very inputs -- the reference's own rounding, the yardstick of the bar."""
+    names = ("rgb", "dist", "alpha", "grad")
+    r64 = dict(zip(names, composite_ref(raw, z, flags, g_rgb, g_dist, torch.float64)))
+    r32 = composite_ref(raw, z, flags, g_rgb, g_dist, torch.float32)
+    e32 = {n: (t.double() - r64[n]).abs().max().item() for n, t in zip(names, r32)}
+    return r64, e32
+
+
+def f32_bar(t_project: float, e_f32: float) -> float:
+    """The bar of the per-ray kernel tests: T_project + 4 E_f32.  T_project is the fixed tolerance
+    the suite already holds that quantity to; E_f32 the plain f32 reference's own error against
+    fp64 on the same inputs.  The factor covers the hardware exp / log / rcp of the 16-lane kernels
+    (a few ulp each against libm's sub-ulp), the scan-tree order of the transmittance product and
+    the butterfly order of the sums: a margin, not a measurement."""
+    return t_project + F32_MARGIN * e_f32
+
+
+def lattice_points(n, seed, lo=0, hi=4):
+    """[3][n] f32 points on the integer lattice {lo .. hi-1}^3: every squared distance is exact in
+    f32, so nearest-neighbour ties are exact ties."""
+    return torch.randint(lo, hi, (3, n), generator=torch.Generator().manual_seed(seed)).float()

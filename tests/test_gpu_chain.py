@@ -137,8 +137,9 @@ def test_chain_gradients_match_per_layer(dev, h16):
 
 # ---- the fused per-ray eval kernel (nerf_render_eval_fused) ----------------------------
 @pytest.mark.parametrize("R,S,flags", [(1024, 128, 0), (333, 64, 0), (257, 32, 2), (130, 16, 1), (97, 128, 4),
-                                       (5, 2, 0)],
-                         ids=["cfg4-S128", "S64-ragged", "S32-white", "S16-distalpha", "S128-relu", "S2-tiny"])
+                                       (5, 2, 0), (9, 4, 3), (21, 8, 4)],
+                         ids=["cfg4-S128", "S64-ragged", "S32-white", "S16-distalpha", "S128-relu", "S2-tiny",
+                              "S4-distalpha-white", "S8-relu"])
 def test_fused_eval_matches_unfused_and_oracle(dev, h16, R, S, flags):
     """One launch (in-kernel samples + encodings, ten linears, heads, composite) against the
     unfused eval path (encode, chain, heads, composite launches) and the fp32 oracle."""
