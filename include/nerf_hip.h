@@ -649,14 +649,15 @@ int nerf_ray_loss_bwd(const float* rgb, const float* rgb_gt, int n_rays, const f
  *   loss_rgb_s = mean over valid elements of clamp(|img1(p) - img2(proj(R pc1 + t))|, 0, 1)
  *   (bilinear, align_corners, zero padding; the rotated point is replaced by (nl, nl, nl)
  *   when -z < nl; valid = |proj| <= 1), only when img1/img2 ([3][h][w]) are given.
- * All operands are device pointers (K, Rt, s1 included).  work: nerf_pair_workspace floats;
+ * All operands are device pointers (K, Rt, s1 included).  work: nerf_pair_workspace floats,
+ * beginning with X [P][3] then Y [P][3] (the rest is scratch; the backward reads X and Y from it);
  * nn: int [2][P]; out3 = {loss_pc, loss_rgb_s, valid element count}. */
 int nerf_pair_workspace(int n_points, int* n_chunks, int64_t* floats);
 int nerf_pair_forward(const float* d1, const float* d2, int h, int w, const float* K, const float* Rt,
                       const float* s1, float nl, const float* img1, const float* img2, float* work, int* nn,
                       float* out3, void* stream);
 /* Backward: upstream scalars go_pc / go_rgbs (device, optional) -> g_d1, g_d2 [P] (optional),
- * g13 = {dR (9, row-major), dt (3), ds1}; gXY: scratch [12P] floats, 8-byte aligned (ABI 14: the
+ * g13 = {dR (9, row-major), dt (3), ds1 (with s1 = NULL: the derivative at s1 = 1)}; gXY: scratch [12P] floats, 8-byte aligned (ABI 14: the
  * gathered-point chamfer gradients as 6P int64 fixed-point sums, order-independent); part13: scratch
  * [13 * ceil(P / 256)] floats.  rgbs_detach_scale: detach_rgbs_scale (training.py:372-375). */
 int nerf_pair_backward(const float* d1, const float* d2, int h, int w, const float* K, const float* Rt,

@@ -448,3 +448,464 @@ def lattice_points(n, seed, lo=0, hi=4):
     """[3][n] f32 points on the integer lattice {lo .. hi-1}^3: every squared distance is exact in
     f32, so nearest-neighbour ties are exact ties."""
     return torch.randint(lo, hi, (3, n), generator=torch.Generator().manual_seed(seed)).float()
+
+
+# ---- guarded outputs of the kernel tests ---------------------------------------------------------
+SENT = 1234.5      # float sentinel (finite: a stray read of it shows as a wrong value, not a NaN)
+GUARD = 64         # elements before and after the payload (payload 16-byte aligned, nerf_hip.h)
+
+
+class Guarded:
+    """A tensor of `shape` inside a sentinel-filled buffer; the payload starts sentinel-filled too."""
+
+    def __init__(self, shape, dev, dtype=torch.float32, fill=SENT):
+        import math
+        n = math.prod(shape)
+        self.buf = torch.full((2 * GUARD + n,), fill, dtype=dtype, device=dev)
+        self.t = self.buf[GUARD:GUARD + n].view(*shape)
+        self.fill = fill
+        assert self.t.data_ptr() % 16 == 0
+
+    def intact(self) -> bool:
+        return bool((self.buf[:GUARD] == self.fill).all()) and bool((self.buf[-GUARD:] == self.fill).all())
+
+    def untouched(self) -> bool:
+        return bool((self.buf == self.fill).all())
+
+
+# ---- the image-pair kernels (csrc/pair.hip): staged fp64 reference and inputs ------------------------
+# The operations of nerf_pair_forward / _backward (include/nerf_hip.h) in plain torch at a dtype, in
+# stages, so that a discontinuous choice is never compared across precisions: the points; the
+# neighbours of given points; the losses and gradients with nn, valid and bad given; the decisions
+# with their distance to the threshold.  An input set is a dict of f32 CPU tensors: h, w, d1 [P],
+# d2 [P], K [4][4], Rt [4][4], s1 [1] or None, img1 / img2 [3][h][w] or None, nl.
+PAIR_NL = 0.01
+PAIR_SHAPES = ((2, 2), (3, 85), (2, 128), (2, 129), (19, 27), (3, 300), (47, 155))
+PAIR_LARGE = (2, 8193)          # P > 2^14: fixed-point scale 2^47, 15 chunks of five 256-point tiles
+PAIR_CAMERAS = ("diag", "principal", "skew")
+PAIR_GAP = 1e-5                 # relative gap below which a neighbour choice is not compared
+PAIR_D_VALID, PAIR_D_BAD = 1e-5, 1e-6    # no point this close to the validity / the nearest-limit threshold
+PAIR_D_CELL, PAIR_D_SIGN = 5e-7, 1e-6    # nor to a bilinear cell edge (in [-1, 1] units), nor |img1 - img2| to 0
+PAIR_COMBOS = dict(both=(1.0, 0.7), pc=(1.0, None), rgbs=(None, 0.7))
+PAIR_T_ELEM = 2.0 ** -23        # x max |ref|: X, Y, g_d1, g_d2 per element
+PAIR_T_G13 = 1e-6               # x the condition sum: every entry of g13
+# seeds of the generic sets; a set whose default seed (1000 h + w) breaks a condition of
+# pair_assert_conditions has another one here
+PAIR_SEEDS = {(3, 85, "principal"): 103085, (2, 128, "diag"): 202128, (19, 27, "principal"): 119027,
+              (3, 300, "principal"): 303300, (47, 155, "diag"): 247155, (47, 155, "principal"): 747155,
+              (47, 155, "skew"): 2547155, (47, 155, "many"): 54}
+
+
+def pair_camera(kind, h, w):
+    """[4][4] camera of the pair tests: |K00| = |K11| = 1.5 at every aspect ("diag"), with a principal
+    point, with skew, and "full": every entry of K[:3] non-zero (inverse4's pivoting, K[2][c] and
+    K[r][3] in the reprojection and its gradient, the translation column of inv(K))."""
+    K = camera_K(4 * h, 4 * w, 3.0 * w, 3.0 * h)[0].clone()
+    if kind in ("principal", "full"):
+        K[0, 2], K[1, 2] = 0.1, -0.07
+    if kind in ("skew", "full"):
+        K[0, 1] = 0.2
+    if kind == "full":
+        K[1, 0], K[2, 0], K[2, 1] = 0.05, 0.02, -0.03
+        K[0, 3], K[1, 3], K[2, 3] = 0.01, -0.02, 0.03
+    assert kind in PAIR_CAMERAS + ("full",), kind
+    return K
+
+
+def pair_pose(t=(0.05, -0.02, 0.3), r=(0.05, -0.03, 0.02)):
+    """Rt [4][4]: a small rotation about a general axis (Rodrigues), the translation of test_gpu_pair."""
+    r = torch.tensor(r, dtype=torch.float64)
+    th = r.norm()
+    k = r / th
+    Kx = torch.tensor([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]], dtype=torch.float64)
+    Rt = torch.eye(4, dtype=torch.float64)
+    Rt[:3, :3] = torch.eye(3, dtype=torch.float64) + torch.sin(th) * Kx + (1 - torch.cos(th)) * (Kx @ Kx)
+    Rt[:3, 3] = torch.tensor(t, dtype=torch.float64)
+    return Rt.float()
+
+
+def pair_generic_inputs(h, w, camera="diag", with_img=True, with_scale=True, seed=None):
+    """Depths in [2, 5], the small rotation, s1 = 1.3, random images."""
+    seed = PAIR_SEEDS.get((h, w, camera), 1000 * h + w) if seed is None else seed
+    g = torch.Generator().manual_seed(seed)
+    P = h * w
+    d1, d2 = 2.0 + 3.0 * torch.rand(P, generator=g), 2.0 + 3.0 * torch.rand(P, generator=g)
+    img1 = torch.rand(3, h, w, generator=g) if with_img else None
+    img2 = torch.rand(3, h, w, generator=g) if with_img else None
+    return dict(h=h, w=w, d1=d1, d2=d2, K=pair_camera(camera, h, w), Rt=pair_pose(),
+                s1=torch.tensor([1.3]) if with_scale else None, img1=img1, img2=img2, nl=PAIR_NL)
+
+
+def pair_large_inputs():
+    """2x8193 without images.  The pose is a tenth of the generic one: two rows of 8193 points are two
+    dense lines, and a query 0.3 away from the other cloud's line is nearly equidistant from many of its
+    points (0.23 % of the queries within a relative gap of 1e-5 at the generic pose, 1 of 16386 here)."""
+    inp = pair_generic_inputs(*PAIR_LARGE, "diag", with_img=False)
+    inp["Rt"] = pair_pose(t=(0.005, -0.002, 0.03), r=(0.005, -0.003, 0.002))
+    return inp
+
+
+def _pair_cast(inp, dtype):
+    return {k: (v.detach().cpu().to(dtype) if torch.is_tensor(v) else v) for k, v in inp.items()}
+
+
+def _pair_pixels(h, w, dtype):
+    from oracle import nerf_oracle as orc
+    return orc.arange_pixels(h, w, dtype=dtype)[1][0]
+
+
+def _pair_unproject(pix, d, Kinv):
+    """transform_to_world: (inv(K) [x d, y d, d, 1])[:3], [P][3]."""
+    hom = torch.stack([pix[:, 0] * d, pix[:, 1] * d, d, torch.ones_like(d)], 1)
+    return (hom @ Kinv.t())[:, :3]
+
+
+def pair_points(inp, dtype):
+    """pc1, pc2, X = R (pc1 / s1) + t, Y = pc2 / s1, each [P][3] at dtype."""
+    c = _pair_cast(inp, dtype)
+    pix = _pair_pixels(c["h"], c["w"], dtype)
+    Kinv = torch.linalg.inv(c["K"])
+    pc1, pc2 = _pair_unproject(pix, c["d1"], Kinv), _pair_unproject(pix, c["d2"], Kinv)
+    s = 1.0 if c["s1"] is None else c["s1"]
+    return dict(pc1=pc1, pc2=pc2, X=(pc1 / s) @ c["Rt"][:3, :3].t() + c["Rt"][:3, 3], Y=pc2 / s)
+
+
+def pair_dist64(Q, R, idx):
+    """fp64 |Q_i - R_idx(i)| in the summation order of pair_neighbours."""
+    Q, R = Q.detach().cpu().double(), R.detach().cpu().double()[idx.long()]
+    d = Q - R
+    return ((d[:, 0] ** 2 + d[:, 1] ** 2) + d[:, 2] ** 2).sqrt()
+
+
+def pair_dist32(Q, R, idx):
+    """The kernel's f32 distance expression (k_nn_part: every operation rounded, no contraction)."""
+    d = Q.detach().cpu().float() - R.detach().cpu().float()[idx.long()]
+    return ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).sqrt()
+
+
+def pair_neighbours(Q, R, block=512, device=None):
+    """Neighbours of the queries Q [P][3] among R [P'][3] as given, in fp64, in row blocks (no P x P'
+    matrix is held): (best distance, first index attaining it, relative gap to the best distance at
+    any other index; 0 on an exact tie).  device: where the reduction runs (torch, float64)."""
+    dev = torch.device("cpu") if device is None else device
+    Q, R = Q.detach().to(dev, torch.float64), R.detach().to(dev, torch.float64)
+    rx, ry, rz = R[:, 0][None], R[:, 1][None], R[:, 2][None]
+    best, first, second = [], [], []
+    for i0 in range(0, Q.shape[0], block):
+        q = Q[i0:i0 + block]
+        D = (((q[:, 0:1] - rx) ** 2 + (q[:, 1:2] - ry) ** 2) + (q[:, 2:3] - rz) ** 2).sqrt_()
+        b, f = D.min(1)
+        D.scatter_(1, f[:, None], float("inf"))
+        best.append(b)
+        first.append(f)
+        second.append(D.min(1).values)
+    best, first, second = torch.cat(best).cpu(), torch.cat(first).cpu(), torch.cat(second).cpu()
+    gap = torch.where(second == best, torch.zeros_like(best), (second - best) / best)
+    return best, first, gap
+
+
+def pair_decisions(inp, dtype=torch.float64):
+    """The decisions of the reprojection (in fp64 unless a dtype is given) with their distance to the threshold: bad (-q_z
+    against nl), valid (max(|p_x|, |p_y|) against 1); for valid unclamped points the distance of p to
+    the nearest bilinear cell edge of img2 (the sample's gradient jumps there) and min |img1 - img2|
+    (the sign of the difference).  Without images: no rgb_s term, nothing valid."""
+    from oracle import nerf_oracle as orc
+    c = _pair_cast(inp, dtype)
+    h, w, P = c["h"], c["w"], c["h"] * c["w"]
+    pts = pair_points(inp, dtype)
+    q = pts["pc1"] @ c["Rt"][:3, :3].t() + c["Rt"][:3, 3]
+    m_bad = -q[:, 2] - c["nl"]
+    bad = m_bad < 0
+    q = torch.where(bad[:, None], torch.full_like(q, c["nl"]), q)
+    h3 = q @ c["K"][:3, :3].t() + c["K"][:3, 3]
+    p = h3[:, :2] / h3[:, 2:]
+    mx = p.abs().amax(1)
+    valid = mx <= 1
+    out = dict(bad=bad, valid=valid, d_bad=m_bad.abs(), d_valid=(mx - 1).abs(), p=p, d_cell=float("inf"),
+               d_sign=float("inf"))
+    if c["img1"] is None:
+        out["valid"] = torch.zeros(P, dtype=torch.bool)
+        return out
+    live = valid & ~bad
+    if bool(live.any()):
+        ij = (p[live] + 1) * 0.5 * torch.tensor([w - 1, h - 1], dtype=dtype)
+        out["d_cell"] = ((ij - ij.round()).abs() * 2 / torch.tensor([w - 1, h - 1], dtype=dtype)).min().item()
+        pix = _pair_pixels(h, w, dtype)
+        e = orc.grid_values(c["img1"][None], pix[None])[0] - orc.grid_values(c["img2"][None], p[None])[0]
+        out["d_sign"] = e[live].abs().min().item()
+    return out
+
+
+def pair_assert_conditions(inp, dec=None):
+    """The conditions under which the kernel's f32 decisions are the fp64 ones (ISSUE section 3)."""
+    dec = pair_decisions(inp) if dec is None else dec
+    if inp["img1"] is None:
+        return dec
+    assert dec["d_valid"].min().item() >= PAIR_D_VALID, ("validity threshold", dec["d_valid"].min().item())
+    assert dec["d_bad"].min().item() >= PAIR_D_BAD, ("nearest-limit threshold", dec["d_bad"].min().item())
+    assert dec["d_cell"] >= PAIR_D_CELL, ("bilinear cell edge", dec["d_cell"])
+    assert dec["d_sign"] >= PAIR_D_SIGN, ("sign of img1 - img2", dec["d_sign"])
+    return dec
+
+
+def pair_loss_ref(inp, nn, valid, bad, go_pc=1.0, go_rgbs=None, detach=False, dtype=torch.float64, _wrong=None):
+    """go_pc (mean |X - Y[a]| + mean |Y - X[b]|) + go_rgbs rgb_s with nn = (a, b) [2][P], valid and bad
+    given, and its autograd at dtype; R, t and s1 are expanded to per-point leaves, so g13 = {dR, dt,
+    ds1} is the sum of the per-point gradients and cond13 the sum of their absolute values.
+    detach: rgbs_detach_scale (pc1 of the reprojection carries no gradient).  A weight of None leaves
+    its term out.  _wrong: the wrong kernels of tests/test_pair_reference_cpu.py, nothing else."""
+    from oracle import nerf_oracle as orc
+    c = _pair_cast(inp, dtype)
+    h, w, P = c["h"], c["w"], c["h"] * c["w"]
+    leaf = lambda t: t.clone().requires_grad_(True)      # noqa: E731
+    d1, d2 = leaf(c["d1"]), leaf(c["d2"])
+    Rp, tp = leaf(c["Rt"][:3, :3].expand(P, 3, 3)), leaf(c["Rt"][:3, 3].expand(P, 3))
+    sp = leaf((torch.ones(1, dtype=dtype) if c["s1"] is None else c["s1"]).expand(P, 1))      # NULL: ds1 at s1 = 1
+    pix = _pair_pixels(h, w, dtype)
+    Kinv = torch.linalg.inv(c["K"])
+    pc1, pc2 = _pair_unproject(pix, d1, Kinv), _pair_unproject(pix, d2, Kinv)
+    X = torch.einsum("pij,pj->pi", Rp, pc1 / sp) + tp
+    Y = pc2 / sp
+    a, b = nn[0].long(), nn[1].long()
+    Ya = Y[a]
+    if _wrong == "dropped_term":                         # one scattered term missing
+        Ya = torch.where((torch.arange(P) == P // 2)[:, None], Ya.detach(), Ya)
+    pc = torch.linalg.norm(X - Ya, dim=1).mean() + torch.linalg.norm(Y - X[b], dim=1).mean()
+    total = torch.zeros((), dtype=dtype)
+    if go_pc is not None:
+        total = total + go_pc * pc
+    rgb_s = torch.zeros((), dtype=dtype)
+    if c["img1"] is not None:
+        K3 = c["K"][:3]
+        pr = pc1.detach() if (detach and _wrong != "scale_attached") else pc1
+        q = torch.einsum("pij,pj->pi", Rp, pr) + tp
+        nlq = torch.full_like(q, c["nl"])
+        q = torch.where(bad[:, None], nlq + (q - q.detach()) if _wrong == "clamped_gradient" else nlq, q)
+        h3 = q @ K3[:, :3].t() + K3[:, 3]
+        if _wrong == "diagonal_K":                       # the gradient as if K were diagonal
+            hd = q * torch.diagonal(K3[:, :3])
+            h3 = hd + (h3 - hd).detach()
+        p_re = h3[:, :2] / h3[:, 2:]
+        rgb1 = orc.grid_values(c["img1"][None], pix[None])
+        rgb2 = orc.grid_values(c["img2"][None], p_re[None])
+        rgb_s = orc.rgb_s_loss_ref(rgb1.view(1, h, w, 3), rgb2.view(1, h, w, 3), valid.view(1, h, w, 1))
+        if go_rgbs is not None:
+            total = total + go_rgbs * rgb_s
+    if total.requires_grad:
+        total.backward()
+    z = lambda t: torch.zeros_like(t) if t.grad is None else t.grad      # noqa: E731
+    gR, gt = z(Rp), z(tp)
+    gs = z(sp)
+    g13 = torch.cat([gR.sum(0).reshape(9), gt.sum(0), gs.sum().reshape(1)])
+    cond13 = torch.cat([gR.abs().sum(0).reshape(9), gt.abs().sum(0), gs.abs().sum().reshape(1)])
+    return dict(pc=pc.detach(), rgb_s=rgb_s.detach(), g_d1=z(d1), g_d2=z(d2), g13=g13, cond13=cond13, gR_pp=gR, gt_pp=gt)
+
+
+class PairRef:
+    """The checks of one input set, shared by the GPU module (the kernels' outputs) and the CPU module
+    (a torch-f32 emulation and its wrong variants).  Bars: |got - f64| <= T + 4 E_f32 (f32_bar), E_f32
+    the max-norm error of the f32 run of the staged reference against its f64 run on the same inputs,
+    nn, valid and bad.  worst[name]: the largest |got - f64| / (T + E_f32) seen."""
+
+    def __init__(self, inp, device=None, generic=True):
+        self.inp, self.P, self.device, self.generic = inp, inp["h"] * inp["w"], device, generic
+        self.with_img = inp["img1"] is not None
+        self.pts64, self.pts32 = pair_points(inp, torch.float64), pair_points(inp, torch.float32)
+        self.dec = pair_assert_conditions(inp)
+        self.worst = {}
+        self._refs = {}
+
+    def bar(self, name, got, r64, r32, T, where):
+        got, r32 = got.detach().cpu().double().reshape(r64.shape), r32.double()
+        assert bool(torch.isfinite(got).all()), f"{where}: {name} not finite"
+        e32 = (r32 - r64).abs().max().item() if r64.numel() else 0.0
+        err = (got - r64).abs()
+        T = torch.as_tensor(T, dtype=torch.float64).expand_as(err)
+        lim = T + F32_MARGIN * e32
+        den = T + e32
+        ratio = torch.where(den > 0, err / den.clamp_min(1e-300), torch.where(err > 0, float("inf"), 0.0).double())
+        r = ratio.max().item() if ratio.numel() else 0.0
+        self.worst[name] = max(self.worst.get(name, 0.0), r)
+        print(f"{where} {name}: |got-f64| {err.max().item():.3e}  E_f32 {e32:.3e}  T {T.max().item():.3e}  ratio {r:.3f}")
+        bad = (err > lim).nonzero().flatten()
+        assert bad.numel() == 0, (f"{where}: {name}: {bad.numel()} elements over the bar, first {bad[:4].tolist()}: "
+                                  f"|got - f64| = {err.flatten()[bad[:4]].tolist()} > T + 4 * {e32:.3e} "
+                                  f"= {lim.flatten()[bad[:4]].tolist()}")
+
+    def check_points(self, X, Y, where=""):
+        for name, got in (("X", X), ("Y", Y)):
+            r64 = self.pts64[name]
+            self.bar(name, got, r64, self.pts32[name], PAIR_T_ELEM * r64.abs().max().item(), where)
+
+    def check_nn(self, X, Y, nn, where=""):
+        """nn [2][P] against the fp64 neighbours of the very points X, Y -> per direction (best, first, gap)."""
+        P, out = self.P, []
+        nn = nn.detach().cpu().view(2, P).long()
+        assert bool(((nn >= 0) & (nn < P)).all()), f"{where}: nn outside [0, P)"
+        for z, (Q, R) in enumerate(((X, Y), (Y, X))):
+            best, first, gap = pair_neighbours(Q, R, device=self.device)
+            d = pair_dist64(Q, R, nn[z])
+            worse = (d > best * (1 + PAIR_GAP)).nonzero().flatten()
+            assert worse.numel() == 0, (f"{where}: direction {z}: {worse.numel()} queries with a neighbour farther than "
+                                        f"the best, first {worse[:4].tolist()}")
+            strict = gap > PAIR_GAP
+            wrong = (strict & (nn[z] != first)).nonzero().flatten()
+            assert wrong.numel() == 0, (f"{where}: direction {z}: {wrong.numel()} wrong neighbours, first at "
+                                        f"{wrong[:4].tolist()}: {nn[z][wrong[:4]].tolist()} vs {first[wrong[:4]].tolist()}")
+            if self.generic:
+                assert int((~strict).sum()) <= 1e-3 * P, f"{where}: direction {z}: {int((~strict).sum())} near-ties"
+            out.append((best, first, gap))
+        return out
+
+    def refs(self, nn, combo, detach):
+        """(f64, f32) runs of the staged reference with this nn."""
+        nn = nn.detach().cpu().view(2, self.P).long()
+        key = (combo, bool(detach), hash(nn.numpy().tobytes()))
+        if key not in self._refs:
+            go_pc, go_rgbs = PAIR_COMBOS[combo]
+            self._refs[key] = tuple(pair_loss_ref(self.inp, nn, self.dec["valid"], self.dec["bad"], go_pc, go_rgbs, detach, dt)
+                                    for dt in (torch.float64, torch.float32))
+        return self._refs[key]
+
+    def check_out3(self, out3, nn, where=""):
+        out3 = out3.detach().cpu()
+        r64, r32 = self.refs(nn, "both" if self.with_img else "pc", False)
+        self.bar("out3[0]", out3[0], r64["pc"], r32["pc"], 1e-5 * r64["pc"].abs().item(), where)
+        self.bar("out3[1]", out3[1], r64["rgb_s"], r32["rgb_s"], 1e-5 * r64["rgb_s"].abs().item() + 1e-7, where)
+        n_valid = int(self.dec["valid"].sum())
+        assert out3[2].item() == 3.0 * n_valid, f"{where}: out3[2] = {out3[2].item()} with {n_valid} valid points"
+        if not self.with_img or n_valid == 0:
+            assert out3[1].item() == 0.0, f"{where}: rgb_s without a valid point"
+
+    def check_grads(self, g, nn, combo, detach, where=""):
+        """g: dict(g_d1 [P], g_d2 [P], g13 [13]) of one backward."""
+        r64, r32 = self.refs(nn, combo, detach)
+        where = f"{where} {combo} detach={int(detach)}"
+        for name in ("g_d1", "g_d2"):
+            self.bar(name, g[name], r64[name], r32[name], PAIR_T_ELEM * r64[name].abs().max().item(), where)
+        g13 = g["g13"].detach().cpu()
+        for name, sl in (("dR", slice(0, 9)), ("dt", slice(9, 12)), ("ds1", slice(12, 13))):
+            self.bar(name, g13[sl], r64["g13"][sl], r32["g13"][sl], PAIR_T_G13 * r64["cond13"][sl], where)
+        if combo == "rgbs":
+            assert bool((g["g_d2"].detach().cpu() == 0).all()), f"{where}: g_d2 from rgb_s alone"
+            live = self.dec["valid"] & ~self.dec["bad"]
+            dead = ~live
+            if not detach:
+                assert bool((g["g_d1"].detach().cpu()[dead] == 0).all()), f"{where}: g_d1 of an invalid or clamped point"
+            else:
+                assert bool((g["g_d1"].detach().cpu() == 0).all()), f"{where}: g_d1 through a detached scale"
+                if bool(live.any()):
+                    assert g13[:9].abs().max().item() > 0 and g13[9:12].abs().max().item() > 0, f"{where}: dR, dt"
+            assert g13[12].item() == 0.0, f"{where}: ds1 from rgb_s alone"
+            if not bool(live.any()):
+                assert bool((g13 == 0).all()) and bool((g["g_d1"].detach().cpu() == 0).all()), f"{where}: nothing valid"
+
+    def report(self, test):
+        for name, r in self.worst.items():
+            report_err(test, name, r)
+
+
+# ---- crafted input sets of the pair tests ------------------------------------------------------------
+def pair_tie_inputs(case):
+    """Exact nearest-neighbour ties (diagonal K, Rt the identity, no scale, no images) -> (inputs,
+    tied X queries, the first index each must return).
+    "chunks" 3x300: d2 equal in rows 0 and 2 per column, row 1 far: every query of X's row 1 (y = 0) is
+    equidistant from Y[c'] and Y[2w + c'], which lie in different chunks (k_nn_final).
+    "tile" 3x129 and "tiles" 2x8193 (w - 1 a power of two: x(c) = -x(w - 1 - c) exactly): Y is far
+    except columns c0 and w - 1 - c0 of row 0 at one depth; the centre-column queries (x = 0) are
+    equidistant from both -- inside one 256-point tile (40, 88), and in two tiles of the chunk
+    3840..5119 (3896, 4296)."""
+    h, w = dict(chunks=(3, 300), tile=(3, 129), tiles=PAIR_LARGE)[case]
+    g = torch.Generator().manual_seed(41 + h * w)
+    d1 = 2.0 + 3.0 * torch.rand(h, w, generator=g)
+    if case == "chunks":
+        row = 2.0 + 3.0 * torch.rand(w, generator=g)
+        d2 = torch.stack([row, torch.full((w,), 50.0), row])
+        tied = torch.arange(w, 2 * w)
+        first = None                                     # the reference's first index, < w
+    else:
+        c0 = 40 if case == "tile" else 3896
+        d2 = 1000.0 + 50.0 * torch.rand(h, w, generator=g)
+        d2[0, c0] = d2[0, w - 1 - c0] = 3.0
+        tied = torch.arange(h) * w + (w - 1) // 2
+        first = torch.full((h,), c0)
+    inp = dict(h=h, w=w, d1=d1.reshape(-1), d2=d2.reshape(-1), K=pair_camera("diag", h, w), Rt=torch.eye(4), s1=None,
+               img1=None, img2=None, nl=PAIR_NL)
+    return inp, tied, first
+
+
+def pair_assert_ties(X, Y, tied, first_want, neigh):
+    """The premise of a tie case on the points X, Y as given: every query of `tied` has an exact tie
+    (fp64 gap 0, and the f32 distance expression of the kernel bitwise equal at two indices at least);
+    -> the first index of each."""
+    best, first, gap = neigh
+    assert tied.numel() >= 1
+    assert bool((gap[tied] == 0).all()), "a tie is not exact in fp64"
+    Xq, Yr = X.detach().cpu().float()[tied], Y.detach().cpu().float()
+    d = Xq[:, None, :] - Yr[None, :, :]
+    D = ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]).sqrt()
+    n_min = (D == D.min(1, keepdim=True).values).sum(1)
+    assert bool((n_min >= 2).all()), "a tie is not exact in the f32 expression"
+    assert torch.equal(D.argmin(1), first[tied]), "f32 and fp64 disagree on the first index"
+    if first_want is not None:
+        assert torch.equal(first[tied], first_want)
+    return first[tied]
+
+
+def pair_many_to_one_inputs(h, w):
+    """d2 about 1e3 except one pixel near the X cloud: every X query chooses it (P scattered terms on one
+    point).  Generic d1, pose and scale; images at 47x155, none at the large shape."""
+    inp = pair_generic_inputs(h, w, "diag", with_img=(h, w) != PAIR_LARGE, seed=PAIR_SEEDS.get((h, w, "many"), 7 + h))
+    g = torch.Generator().manual_seed(h + w)
+    hot = (h // 2) * w + w // 2
+    inp["d2"] = 1000.0 + 50.0 * torch.rand(h * w, generator=g)
+    inp["d2"][hot] = 3.5
+    return inp, hot
+
+
+def pair_coincident_inputs():
+    """19x27, Rt the identity, no scale, no images, d1 == d2 on the patch rows 5..10 x columns 5..15:
+    X_i == Y_i there (distance 0: the d > 0 branches) -> (inputs, patch indices)."""
+    h, w = 19, 27
+    inp = pair_generic_inputs(h, w, "diag", with_img=False, with_scale=False, seed=77)
+    inp["Rt"] = torch.eye(4)
+    m = torch.zeros(h, w, dtype=torch.bool)
+    m[5:11, 5:16] = True
+    patch = m.reshape(-1).nonzero().flatten()
+    inp["d2"][patch] = inp["d1"][patch]
+    return inp, patch
+
+
+def pair_clamped_inputs():
+    """19x27 (P = 513) with |K00| = |K11| = 0.8 and d1 = nl on the first 256 points (the whole first
+    workgroup): rotated and translated they lie behind the camera (bad), and (nl, nl, nl) projects to
+    (-0.8, 0.8): valid.  The forward counts them, the backward gives them nothing."""
+    h, w = 19, 27
+    inp = pair_generic_inputs(h, w, "diag", seed=PAIR_SEEDS.get("clamped", 91))
+    inp["K"] = camera_K(h, w, 0.4 * w, 0.4 * h)[0].clone()
+    inp["d1"][:256] = PAIR_NL
+    return inp, torch.arange(256)
+
+
+def pair_no_valid_inputs():
+    """12x17: a sideways translation puts every projection outside [-1, 1]."""
+    inp = pair_generic_inputs(12, 17, "diag", seed=12)
+    inp["Rt"] = pair_pose(t=(20.0, -0.02, 0.3))
+    return inp
+
+
+def pair_input_sets():
+    """Every input set of tests/test_gpu_pair_fp64.py with images or a decision in it: (name, inputs)."""
+    for h, w in PAIR_SHAPES:
+        for cam in PAIR_CAMERAS:
+            yield f"{h}x{w}-{cam}", pair_generic_inputs(h, w, cam)
+    for h, w in ((19, 27), (3, 85)):
+        yield f"{h}x{w}-full", pair_generic_inputs(h, w, "full")
+    yield "large", pair_large_inputs()
+    for case in ("chunks", "tile", "tiles"):
+        yield f"tie-{case}", pair_tie_inputs(case)[0]
+    yield "many-47x155", pair_many_to_one_inputs(47, 155)[0]
+    yield "many-large", pair_many_to_one_inputs(*PAIR_LARGE)[0]
+    yield "coincident", pair_coincident_inputs()[0]
+    yield "clamped", pair_clamped_inputs()[0]
+    yield "no-valid", pair_no_valid_inputs()

@@ -42,25 +42,32 @@ def _rel(a, b):
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
 
 
-@pytest.mark.parametrize("res,with_rgbs,with_scale", [((12, 17), True, True), ((47, 155), True, True),
-                                                      ((20, 30), False, False)])
-def test_pair_losses_match_oracle(dev, res, with_rgbs, with_scale):
+PAIR_CASES = [((12, 17), True, True), ((47, 155), True, True), ((20, 30), False, False)]
+
+
+def _inputs(res, with_rgbs, with_scale):
     g = torch.Generator().manual_seed(res[0])
     h, w = res
     K = camera_K(4 * h, 4 * w, 3.0 * w, 3.0 * w)
     d1 = 2.0 + 3.0 * torch.rand(1, 1, h, w, generator=g)
     d2 = 2.0 + 3.0 * torch.rand(1, 1, h, w, generator=g)
-    d1[0, 0, 0, :3] = 0.01                                   # the nearest_limit floor
-    th = 0.05
+    d1[0, 0, 0, :3] = 0.01                                   # at the nearest_limit floor: with t_z = 0.3 these three
+    th = 0.05                                                # points land behind the camera (-z < nl)
     Rt = torch.eye(4).unsqueeze(0)
     Rt[0, :3, :3] = torch.tensor([[1.0, 0, 0], [0, torch.cos(torch.tensor(th)), -torch.sin(torch.tensor(th))],
                                   [0, torch.sin(torch.tensor(th)), torch.cos(torch.tensor(th))]])
     Rt[0, :3, 3] = torch.tensor([0.05, -0.02, 0.1])
-    Rt[0, 2, 3] = 0.3                                        # pushes some points behind the camera (-z < nl)
+    Rt[0, 2, 3] = 0.3                                        # every other point stays in front of it
     s1 = torch.tensor([1.3]) if with_scale else None
     img1 = torch.rand(1, 3, h, w, generator=g) if with_rgbs else None
     img2 = torch.rand(1, 3, h, w, generator=g) if with_rgbs else None
-    nl = 0.01
+    return d1, d2, K, Rt, s1, img1, img2, 0.01
+
+
+@pytest.mark.parametrize("res,with_rgbs,with_scale", PAIR_CASES)
+def test_pair_losses_match_oracle(dev, res, with_rgbs, with_scale):
+    h, w = res
+    d1, d2, K, Rt, s1, img1, img2, nl = _inputs(res, with_rgbs, with_scale)
 
     # oracle, float64 with autograd
     o = [x.double().clone().requires_grad_(True) if x is not None else None for x in (d1, d2, Rt, s1)]

@@ -8,37 +8,17 @@ is the fixed tolerance the suite already holds that quantity to; E_f32 is the er
 operation in plain f32 torch on the CPU against fp64, on the very same inputs and tensor -- never
 a number taken from the kernels.  Every output is a slice of a larger buffer filled with a
 sentinel, the payload 256 bytes in; the sentinel before and after it must survive every call."""
-import math
-
 import pytest
 import torch
 
 from model import _hip
 from oracle import nerf_oracle as orc
 from tests import helpers as H
+from tests.helpers import Guarded
 
 pytestmark = pytest.mark.gpu
 
-SENT = 1234.5      # float sentinel (finite: a stray read of it shows as a wrong value, not a NaN)
-GUARD = 64         # elements before and after the payload (payload 16-byte aligned, nerf_hip.h)
 R = H.COMPOSITE_R
-
-
-class Guarded:
-    """A tensor of `shape` inside a sentinel-filled buffer; the payload starts sentinel-filled too."""
-
-    def __init__(self, shape, dev, dtype=torch.float32, fill=SENT):
-        n = math.prod(shape)
-        self.buf = torch.full((2 * GUARD + n,), fill, dtype=dtype, device=dev)
-        self.t = self.buf[GUARD:GUARD + n].view(*shape)
-        self.fill = fill
-        assert self.t.data_ptr() % 16 == 0
-
-    def intact(self) -> bool:
-        return bool((self.buf[:GUARD] == self.fill).all()) and bool((self.buf[-GUARD:] == self.fill).all())
-
-    def untouched(self) -> bool:
-        return bool((self.buf == self.fill).all())
 
 
 def _rand(*s, g=None):
