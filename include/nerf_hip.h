@@ -500,7 +500,8 @@ int nerf_encode_bwd(const float* pts_o, const float* pts_d, const float* view, c
  * dst_s / dst_ts (optional): the whole padded dst / dst_t as bf16x3 split images, the B
  * operand format of GEMM precision mode 1 (hi, mid, lo planes; ld_dst, ld_t % 8 == 0).
  * In GEMM precision mode 2 the same buffers receive the fp16 pair form instead: each image
- * row r scaled by 2^e_r (row max -> [2^14, 2^15)), planes 0 / 1 = fp16 hi / lo, and e_r as
+ * row r scaled by 2^e_r (row max -> [2^14, 2^15); e_r = 0 for a zero row, 140 for a subnormal
+ * row maximum), planes 0 / 1 = fp16 hi / lo (hi = fp16(x 2^e_r), lo = fp16(x 2^e_r - hi)), and e_r as
  * an int32 in the first word of plane 2's chunk 0 of that row (u16 index
  * ((2*K/8)*rows + r)*8).
  * dst_cs / dst_cts (optional, mode 2 only; ABI 13): the CHAIN images of dst / dst_t -- the
@@ -535,7 +536,7 @@ int nerf_pack_weights(const nerf_pack_desc* descs, int n, void* stream);
  * slots 8-13, 1 - beta1, 1.0}: 1 - beta1 / 1 - beta2 rounded once from the caller's doubles and
  * the bias corrections lr / (1 - beta1^t), sqrt(1 - beta2^t) taken in double, as torch forms
  * them (slot 15 != 1: the doubles are ignored and derived from the f32 slots; slot 6 == 0:
- * 1 - beta2 from the f32 beta2).  The update uses step + 1 and the last workgroup to finish
+ * 1 - beta2 formed on the device from beta2 -- the double while slot 15 == 1, else the f32 slot).  The update uses step + 1 and the last workgroup to finish
  * stores it back (one launch; a captured graph replays the correct bias corrections).
  * hyper[7] is a completion counter: zero it once. */
 int nerf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
@@ -556,14 +557,22 @@ int nerf_chamfer_nn(const float* x, int p, const float* y, int q, int64_t* idx, 
  *   of arange_pixels (common.py:13-40; pixels [R][2], needs width*height == n_pix) and the
  *   colours img.view(3, H*W)[:, idx]^T (rgb [R][3], img = [3][H][W]).  One workgroup.
  *   Requires R <= NERF_SAMPLE_MAX_RAYS and n_pix >= 2R.  status (optional, int) receives
- *   the number of draw rounds used, 0 if NERF_SAMPLE_MAX_ROUNDS did not suffice. */
+ *   the number of draw rounds used, 0 if NERF_SAMPLE_MAX_ROUNDS did not suffice.
+ *   The draw rule (what "deterministic" means; tests/helpers.py sample_rays_ref is this rule in
+ *   numpy): the Philox key is (seed & 0xffffffff, seed >> 32).  In round k = 0, 1, ... every ray
+ *   slot s without a value draws v = floor(u * n_pix / 2^64), u = (w0 << 32) | w1 with (w0, w1,
+ *   ..) = Philox-4x32-10 at counter (s, k, 0x5a4d, 0).  A value belongs to the smallest
+ *   (round, slot) that drew it; every other slot that drew it draws again in the next round.
+ *   idx[s] is slot s's value, status the number of rounds until every slot has one. */
 #define NERF_SAMPLE_MAX_RAYS 4096
 #define NERF_SAMPLE_MAX_ROUNDS 64
 int nerf_sample_rays(int n_pix, int n_rays, uint64_t seed, int width, int height, const float* img,
                      int64_t* idx, float* pixels, float* rgb, int* status, uint64_t* seed_counter,
                      void* stream);
 /* seed_counter (optional, device uint64): mixed into the Philox key and advanced by one per
- * launch on the device -- successive replays of a captured hipGraph draw new rays. */
+ * launch on the device -- successive replays of a captured hipGraph draw new rays.  With the
+ * counter at c the key words are xored with the low and the high half of
+ * (c + 1) * 0x9E3779B97F4A7C15 mod 2^64. */
 
 /* Batched 4x4 inverse (torch.inverse / linalg.inv_ex, common.py:139-141, training.py:255-257):
  * Gauss-Jordan with partial pivoting, a [n][4][4] -> out [n][4][4]. */
@@ -611,7 +620,9 @@ int nerf_depth_affine_bwd(const float* d, int n, const float* scale, const float
  * (NULL = no depth prior, d_src = 1): cam [R][3] = M[:3,3]; v = M[:3,:3](x,y,1);
  * ray_norm = |v|; ray = v/|v| (NERF_RAYS_NORMALISE) else v; d_src = |M[:3,:3](xd,yd,d)|
  * (divided by |v| without NORMALISE); mask [R] (u8, optional) = isfinite(d_src) & d_src != 0;
- * view [R][3] (optional) = -ray, or 1 with NERF_RAYS_VIEW_ONES (use_ray_dir False). */
+ * view [R][3] (optional) = -ray, or 1 with NERF_RAYS_VIEW_ONES (use_ray_dir False).
+ * Without a depth (depth == NULL) d_src is exactly 1 under either value of NERF_RAYS_NORMALISE --
+ * it is not divided by |v| -- and the backward treats it as a constant. */
 #define NERF_RAYS_NORMALISE 1
 #define NERF_RAYS_VIEW_ONES 2
 int nerf_camera_rays(const float* M, const float* pixels, const float* depth, int n_rays, int flags,

@@ -423,7 +423,8 @@ __global__ __launch_bounds__(CR_THREADS) void k_camera_rays(const float* __restr
         n2 = n2 + v[i] * v[i];
     }
     const float n = sqrtf(n2);
-    float ds = 1.f;
+    const bool normalise = flags & NERF_RAYS_NORMALISE;
+    float ds = 1.f;   // no depth prior: d_src = 1 under either flag (the backward takes it as constant)
     if (depth != nullptr) {
         const float d = depth[r];
         const float xd = x * d, yd = y * d;
@@ -434,9 +435,8 @@ __global__ __launch_bounds__(CR_THREADS) void k_camera_rays(const float* __restr
             q2 = q2 + pi * pi;
         }
         ds = sqrtf(q2);
+        if (!normalise) ds = ds / n;
     }
-    const bool normalise = flags & NERF_RAYS_NORMALISE;
-    if (!normalise) ds = ds / n;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const float di = normalise ? v[i] / n : v[i];

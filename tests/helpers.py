@@ -909,3 +909,596 @@ def pair_input_sets():
     yield "coincident", pair_coincident_inputs()[0]
     yield "clamped", pair_clamped_inputs()[0]
     yield "no-valid", pair_no_valid_inputs()
+
+
+# ---- the prologue, loss, Adam and pack kernels (csrc/rays.hip, misc.hip): references and inputs ------
+# Plain numpy / torch at a given dtype, written from the text of include/nerf_hip.h and the reference
+# lines it cites.  Each *_refs helper returns the fp64 run and E_f32, the f32 run's own distance to it on
+# the same inputs.  _wrong=...: the wrong kernels of tests/test_prologue_reference_cpu.py, nothing else.
+SAMPLE_CASES = ((2, 2, 1), (2, 3, 3), (33, 62, 1023), (32, 64, 1024), (41, 50, 1025), (2, 2049, 2049),
+                (90, 91, 4095), (64, 128, 4096), (188, 621, 1024))          # (H, W, R)
+SAMPLE_SEED = 20240611
+SAMPLE_MAX_ROUNDS_USED = 20
+MAT4_BATCHES = (1, 63, 64, 65, 130)
+POSE_R_SCALES = (0.0, 1e-25, 1e-7, 1e-3, 0.7, 3.141592653589793 - 1e-3, 4.0)
+POSE_AXIS = (0.48, -0.6, 0.64)                      # a unit vector
+AFFINE_N = (1, 63, 1023, 1024, 1025, 65536, 65537, 66600)
+CAMERA_R = (1, 63, 64, 65, 255, 256, 257, 1023, 1025)
+LOSS_SHAPES = ((1, 1), (21, 21), (22, 22), (341, 341), (342, 342), (1025, 1025), (5, 40), (40, 5))     # (R, n_depth)
+LOSS_MASKS = ("none", "all", "one", "zero")
+ADAM_N = (1, 2, 3, 4, 5, 7, 1023, 1024, 1025, 524288, 524292, 524293, 525315)
+ADAM_HYPER = dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8)
+T_VALUE, T_GRAD = 1e-5, 1e-4                        # the fixed tolerances of tests/test_gpu_rays.py
+
+
+def tree_ceiling(n: int, threads: int) -> float:
+    """The derived ceiling, as a multiple of sum |term|, of an f32 sum of n terms taken as per-thread
+    serial sums of ceil(n / threads) terms, a 6-step wave butterfly and a 16-term serial tail, each
+    addition one rounding, with 4 roundings for forming a term: (ceil(n / threads) + 26) 2^-24.
+    A derivation, not a measurement."""
+    return (-(-n // threads) + 26) * U24
+
+
+def max_bar(t_rel: float, ref, e_f32: float) -> float:
+    """t_rel max|ref| + 4 E_f32 (f32_bar with the project tolerance relative to the largest entry)."""
+    return f32_bar(t_rel * (ref.abs().max().item() if ref.numel() else 0.0), e_f32)
+
+
+def assert_max_bar(name, got, r64, e_f32, t_rel, where="", worst=None, finite=None):
+    """|got - f64| <= t_rel max|ref| + 4 E_f32 over the elements of `finite` (default: all, and then
+    got must be finite everywhere); records |got - f64| / (T + E_f32) in worst[name]."""
+    got, r64 = got.detach().cpu().double().reshape(r64.shape), r64.double()
+    if finite is None:
+        assert bool(torch.isfinite(got).all()), f"{where}: {name} not finite"
+        finite = torch.ones_like(r64, dtype=torch.bool)
+    rf = r64[finite]
+    T = t_rel * (rf.abs().max().item() if rf.numel() else 0.0)
+    err = (got[finite] - rf).abs().max().item() if rf.numel() else 0.0
+    assert err == err, f"{where}: {name} is NaN where the reference is finite"
+    ratio = err / (T + e_f32) if T + e_f32 > 0 else (0.0 if err == 0 else float("inf"))
+    if worst is not None:
+        worst[name] = max(worst.get(name, (0.0, 0.0))[0], ratio), max(worst.get(name, (0.0, 0.0))[1], e_f32)
+    print(f"{where} {name}: |got-f64| {err:.3e}  E_f32 {e_f32:.3e}  T {T:.3e}  ratio {ratio:.3f}")
+    assert err <= f32_bar(T, e_f32), f"{where}: {name}: |got - f64| = {err:.3e} > {T:.3e} + 4 * {e_f32:.3e}"
+
+
+def assert_sum_bar(name, got, ref, cond, ceiling, e_f32=0.0, where="", worst=None):
+    """|got - ref| <= ceiling cond + 4 E_f32 per entry (cond = sum |term| of the entry's fp64 terms)."""
+    got, ref, cond = got.detach().cpu().double().reshape(-1), ref.double().reshape(-1), cond.double().reshape(-1)
+    assert bool(torch.isfinite(got).all()), f"{where}: {name} not finite"
+    err, lim = (got - ref).abs(), ceiling * cond + F32_MARGIN * e_f32
+    den = ceiling * cond + e_f32
+    ratio = torch.where(den > 0, err / den.clamp_min(1e-300), torch.where(err > 0, float("inf"), 0.0).double()).max().item()
+    if worst is not None:
+        worst[name] = max(worst.get(name, (0.0, 0.0))[0], ratio), max(worst.get(name, (0.0, 0.0))[1], e_f32)
+    print(f"{where} {name}: |got-f64| {err.max().item():.3e}  bar {lim.max().item():.3e}  ratio {ratio:.3f}")
+    assert bool((err <= lim).all()), f"{where}: {name}: |got - f64| = {err.tolist()[:16]} > {lim.tolist()[:16]}"
+
+
+def _e32(r32, r64, names):
+    return {n: ((r32[n].double() - r64[n].double()).abs().max().item() if r64[n] is not None and r64[n].numel() else 0.0)
+            for n in names}
+
+
+# ---- the ray sampler -----------------------------------------------------------------------------------
+def philox4x32_10(counter, key):
+    """Philox-4x32-10 (Salmon et al., SC'11) in numpy: counter [..., 4], key [..., 2] (uint32 values)
+    -> [..., 4] uint32.  One round: (hi0, lo0) = M0 * c0, (hi1, lo1) = M1 * c2, c = (hi1 ^ c1 ^ k0, lo1,
+    hi0 ^ c3 ^ k1, lo0), then the key is bumped by the Weyl constants."""
+    import numpy as np
+    c = np.asarray(counter, dtype=np.uint64)
+    k = np.asarray(key, dtype=np.uint64)
+    mask = np.uint64(0xFFFFFFFF)
+    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    c0, c1, c2, c3 = (c[..., i] & mask for i in range(4))
+    k0, k1 = np.broadcast_to(k[..., 0], c0.shape) & mask, np.broadcast_to(k[..., 1], c0.shape) & mask
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = M0 * c0, M1 * c2                       # < 2^64: both factors are below 2^32
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & mask, (p0 >> s32) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + W0) & mask, (k1 + W1) & mask
+    return np.stack([c0, c1, c2, c3], -1).astype(np.uint32)
+
+
+def sample_key(seed: int, counter=None):
+    """The Philox key of nerf_sample_rays: the two halves of the seed, xored with the two halves of
+    (counter + 1) 0x9E3779B97F4A7C15 mod 2^64 when a seed_counter is given."""
+    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    if counter is not None:
+        m = ((counter + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        k0, k1 = k0 ^ (m & 0xFFFFFFFF), k1 ^ (m >> 32)
+    return k0, k1
+
+
+def sample_rays_ref(n_pix, R, seed, counter=None, _wrong=None):
+    """The draw rule of nerf_sample_rays (include/nerf_hip.h): in round k every pending slot s draws
+    v = floor(u n / 2^64), u the first two words (first the high one) of Philox at counter (s, k,
+    0x5a4d, 0); a value belongs to the smallest (round, slot) that drew it, every other drawer draws
+    again -> (idx int64 [R], rounds)."""
+    import numpy as np
+    key = np.array(sample_key(seed, counter), dtype=np.uint64)
+    idx = np.full(R, -1, dtype=np.int64)
+    owned = set()
+    pending = np.arange(R, dtype=np.uint64)
+    rounds = 0
+    while pending.size:
+        assert rounds < 64, "sample_rays_ref: 64 rounds did not suffice"
+        ctr = np.stack([pending, np.full_like(pending, rounds), np.full_like(pending, 0x5a4d), np.zeros_like(pending)], -1)
+        w = philox4x32_10(ctr, key).astype(np.uint64)
+        hi, lo, n = w[:, 0], w[:, 1], np.uint64(n_pix)
+        v = (hi * n + ((lo * n) >> np.uint64(32))) >> np.uint64(32)      # floor(((hi 2^32 + lo) n) / 2^64), n < 2^31
+        again = []
+        order = zip(pending.tolist(), v.tolist())
+        if _wrong == "larger_slot_wins":
+            order = reversed(list(order))
+        for s, val in order:
+            if val in owned:
+                again.append(s)
+            else:
+                owned.add(val)
+                idx[s] = val
+        pending = np.array(sorted(again), dtype=np.uint64)
+        rounds += 1
+    return torch.from_numpy(idx), rounds
+
+
+def pixels_ref(idx, height, width, dtype=torch.float32):
+    """arange_pixels at the drawn indices (common.py:36-39): (2 col / (W - 1) - 1, 2 row / (H - 1) - 1), [R][2]."""
+    idx = idx.long()
+    col, row = (idx % width).to(dtype), (idx // width).to(dtype)
+    return torch.stack([2.0 * col / (width - 1) - 1.0, 2.0 * row / (height - 1) - 1.0], -1)
+
+
+# ---- the 4x4 chain ------------------------------------------------------------------------------------------
+def mat4_edge_batch(n, seed=0):
+    """[n][4][4] f32: well-conditioned random matrices with, cycling over the batch, rigid poses, a
+    permutation matrix (a pivot swap in every column), a zero leading pivot and one matrix with an entry
+    set so that cond is about 1e5 -> (matrices, dict of the indices of each kind)."""
+    g = torch.Generator().manual_seed(100 + seed + n)
+    A = torch.randn(n, 4, 4, generator=g) + 3 * torch.eye(4)
+    kinds = dict(rigid=[], perm=[], zero_pivot=[], ill=[])
+    P = torch.zeros(4, 4)
+    P[0, 1] = P[1, 2] = P[2, 3] = P[3, 0] = 1.0
+    for i in range(n):
+        k = i % 8 if n > 1 else 2
+        if k == 0:
+            A[i] = rigid_c2w(i)
+            kinds["rigid"].append(i)
+        elif k == 1:
+            A[i] = P * (1.0 + 0.25 * (i % 3))
+            kinds["perm"].append(i)
+        elif k == 2:
+            A[i, 0, 0] = 0.0
+            kinds["zero_pivot"].append(i)
+        elif k == 3:
+            A[i] = torch.eye(4) + 0.1 * (A[i] - 3 * torch.eye(4))
+            A[i, 1:, 0] = 0.0
+            A[i, 0, 3] = 300.0                      # a shear a (the determinant stays near 1): cond about a^2
+            kinds["ill"].append(i)
+    return A.contiguous(), kinds
+
+
+def mat4_inv_refs(A, g):
+    """linalg.inv and the gradient of sum(inv(A) g) in fp64, with E_f32 of CPU torch.linalg.inv in f32."""
+    def run(dt):
+        a = A.to(dt).clone().requires_grad_(True)
+        y = torch.linalg.inv(a)
+        y.backward(g.to(dt))
+        return dict(inv=y.detach(), g_a=a.grad)
+    r64, r32 = run(torch.float64), run(torch.float32)
+    return r64, _e32(r32, r64, ("inv", "g_a"))
+
+
+def mat4_mul_refs(A, B, g):
+    def run(dt):
+        a, b = A.to(dt).clone().requires_grad_(True), B.to(dt).clone().requires_grad_(True)
+        c = a @ b
+        c.backward(g.to(dt))
+        return dict(c=c.detach(), g_a=a.grad, g_b=b.grad)
+    r64, r32 = run(torch.float64), run(torch.float32)
+    return r64, _e32(r32, r64, ("c", "g_a", "g_b"))
+
+
+def unproject_refs(K, W, S, g):
+    """M = (inv(S) inv(W)) inv(K) (common.py:139-141) and its three gradients."""
+    def run(dt):
+        ins = [x.to(dt).clone().requires_grad_(True) for x in (K, W, S)]
+        iv = torch.linalg.inv
+        M = (iv(ins[2]) @ iv(ins[1])) @ iv(ins[0])
+        M.backward(g.to(dt))
+        return dict(M=M.detach(), g_K=ins[0].grad, g_W=ins[1].grad, g_S=ins[2].grad)
+    r64, r32 = run(torch.float64), run(torch.float32)
+    return r64, _e32(r32, r64, ("M", "g_K", "g_W", "g_S"))
+
+
+def pose_c2w_ref(r, t, init, g, dtype):
+    """[Exp(r) | t; 0 0 0 1] @ init with Exp(r) = I + sin(th)/th [r]x + (1 - cos th)/th^2 [r]x^2,
+    th = |r| + 1e-15 (include/nerf_hip.h), and the gradient of sum(c2w g) to r and t by autograd."""
+    r = r.detach().to(dtype).clone().requires_grad_(True)
+    t = t.detach().to(dtype).clone().requires_grad_(True)
+    z = torch.zeros((), dtype=dtype)
+    K = torch.stack([torch.stack([z, -r[2], r[1]]), torch.stack([r[2], z, -r[0]]), torch.stack([-r[1], r[0], z])])
+    th = r.norm() + 1e-15
+    R = torch.eye(3, dtype=dtype) + (torch.sin(th) / th) * K + ((1 - torch.cos(th)) / (th * th)) * (K @ K)
+    c2w = torch.cat([torch.cat([R, t[:, None]], 1), torch.tensor([[0, 0, 0, 1]], dtype=dtype)], 0)
+    if init is not None:
+        c2w = c2w @ init.to(dtype)
+    c2w.backward(g.to(dtype))
+    return dict(c2w=c2w.detach(), g_r=r.grad, g_t=t.grad)
+
+
+def pose_c2w_refs(r, t, init, g):
+    r64, r32 = pose_c2w_ref(r, t, init, g, torch.float64), pose_c2w_ref(r, t, init, g, torch.float32)
+    return r64, _e32(r32, r64, ("c2w", "g_r", "g_t")), r32
+
+
+# ---- the depth-prior distortion ------------------------------------------------------------------------------
+def affine32(d, s, t, shift_first):
+    """The f32 torch expression of nerf_depth_affine before the clamp (training.py:259-264, 325-329)."""
+    return (d + t) * s if shift_first else d * s + t
+
+
+def depth_affine_inputs(n, shift_first, lo, seed=0):
+    """d [n] in [0, 8) with s = 0.8, t = -0.25 and, for n >= 63, entries at d = 0 and (lo finite) entries
+    whose f32 affine image is exactly lo (kept: the clamp is y < lo) and the largest d whose image is
+    below lo (clamped), found by scanning the f32 neighbours of the fp64 solution ->
+    dict(d, s, t, g, at_lo, below, zero: index lists)."""
+    gen = torch.Generator().manual_seed(300 + n + seed)
+    d = torch.rand(n, generator=gen) * 8
+    s, t = torch.tensor([0.8]), torch.tensor([-0.25])
+    idx = dict(at_lo=[], below=[], zero=[])
+    if n >= 63:
+        kinds = ("zero",)
+        if lo != float("-inf"):
+            kinds = ("at_lo", "below", "zero")
+            d0 = torch.tensor(lo / s.double().item() - t.double().item() if shift_first
+                              else (lo - t.double().item()) / s.double().item(), dtype=torch.float32)
+            cand = (d0.view(torch.int32) + torch.arange(-32, 33, dtype=torch.int32)).view(torch.float32)
+            img = affine32(cand, s, t, shift_first)
+            assert bool((img == lo).any()) and bool((img < lo).any())
+            d_at, d_below = cand[img == lo][0], cand[img < lo].max()
+        for j, i in enumerate(range(3, n, max(1, n // 7))):
+            kind = kinds[j % len(kinds)]
+            d[i] = d_at if kind == "at_lo" else d_below if kind == "below" else 0.0
+            idx[kind].append(i)
+    return dict(d=d, s=s, t=t, g=torch.randn(n, generator=gen), **idx)
+
+
+def depth_affine_ref(d, s, t, shift_first, lo, g, dtype=torch.float64, _wrong=None):
+    """y = d s + t (shift_first: (d + t) s), y < lo -> lo; g_s, g_t = the sums over the entries not
+    clamped of g dy/ds, g dy/dt, with the sums of |term|.  Which entries are clamped is decided on the
+    f32 expression (the decision is the kernel's own, not a matter of precision)."""
+    if _wrong == "shift_first_swapped":
+        shift_first = not shift_first
+    pre32 = affine32(d, s, t, shift_first)
+    keep = (pre32 >= lo) if _wrong != "clamped_pass" else torch.ones_like(pre32, dtype=torch.bool)
+    dd, ss, tt, gg = (x.to(dtype) for x in (d, s, t, g))
+    pre = (dd + tt) * ss if shift_first else dd * ss + tt
+    y = torch.where(pre32 < lo, torch.full_like(pre, lo), pre)
+    ts = gg * ((dd + tt) if shift_first else dd) * keep
+    tt_ = gg * (ss if shift_first else torch.ones_like(ss)) * keep
+    return dict(y=y, g_s=ts.sum(), g_t=tt_.sum(), cond_s=ts.abs().sum(), cond_t=tt_.abs().sum(), keep=keep)
+
+
+def f32_tree_sum(terms, threads=1024):
+    """An f32 sum in the order of the one-workgroup kernels (per-thread strided serial sums, then a
+    pairwise tree): the honest f32 evaluation the CPU module holds to tree_ceiling."""
+    x = terms.float().reshape(-1)
+    n = x.numel()
+    pad = (-n) % threads
+    x = torch.cat([x, x.new_zeros(pad)]).view(-1, threads)
+    acc = torch.zeros(threads)
+    for row in x:
+        acc = acc + row
+    while acc.numel() > 1:
+        acc = acc[0::2] + acc[1::2]
+    return acc[0]
+
+
+# ---- camera rays ------------------------------------------------------------------------------------------
+def camera_inputs(R, seed=0, nonfinite=False):
+    """M [4][4] (a rigid pose, a 1.7 scale and a pinhole camera through the fp64 inverses), pixels [R][2]
+    in [-1, 1], depth [R] in [1, 8] with zeros and negatives (and, nonfinite, one +inf and one NaN when R
+    >= 4), five upstream gradients -> dict."""
+    gen = torch.Generator().manual_seed(500 + R + seed)
+    K = camera_K(188, 621, 362.5, 362.5)[0].double()
+    S = torch.eye(4, dtype=torch.float64)
+    S[:3, :3] *= 1.7
+    iv = torch.linalg.inv
+    M = ((iv(S) @ iv(torch.inverse(rigid_c2w(3)).double())) @ iv(K)).float()
+    pix = torch.rand(R, 2, generator=gen) * 2 - 1
+    depth = 1.0 + 7.0 * torch.rand(R, generator=gen)
+    kinds = dict(zero=list(range(0, R, 5)), neg=[i for i in range(2, R, 7) if i % 5], inf=[], nan=[])
+    depth[kinds["zero"]] = 0.0
+    depth[kinds["neg"]] = -depth[kinds["neg"]]
+    if nonfinite and R >= 4:
+        depth[1], depth[3] = float("inf"), float("nan")
+        kinds["inf"], kinds["nan"] = [1], [3]
+        kinds["neg"] = [i for i in kinds["neg"] if i not in (1, 3)]
+        kinds["zero"] = [i for i in kinds["zero"] if i not in (1, 3)]
+    rn = lambda *s: torch.randn(*s, generator=gen)      # noqa: E731
+    return dict(M=M, pix=pix, depth=depth, g_cam=rn(R, 3), g_ray=rn(R, 3), g_view=rn(R, 3), g_norm=rn(R), g_dsrc=rn(R),
+                kinds=kinds)
+
+
+def camera_rays_ref(M, pix, depth, flags, dtype, grads=None, _wrong=None):
+    """nerf_camera_rays by its header: cam = M[:3, 3]; v = M[:3, :3] (x, y, 1); ray_norm = |v|; ray =
+    v / |v| (flag 1) else v; d_src = |M[:3, :3] (x d, y d, d)|, divided by |v| without flag 1; d_src = 1
+    without a depth under either flag; view = -ray, or 1 with flag 2; mask = isfinite(d_src) & d_src != 0.
+    grads: dict of the upstream gradients (g_cam, g_ray, g_view, g_norm, g_dsrc; a missing one is
+    absent) -> also gM [4][4], its per-entry sum of |per-ray term| condM, and g_depth [R], by autograd
+    with M expanded to one leaf per ray."""
+    R = pix.shape[0]
+    Mp = M.detach().to(dtype).expand(R, 4, 4).clone().requires_grad_(True)
+    x, y = pix[:, 0].to(dtype), pix[:, 1].to(dtype)
+    A = Mp[:, :3, :3]
+    cam = Mp[:, :3, 3]
+    v = A[:, :, 0] * x[:, None] + A[:, :, 1] * y[:, None] + A[:, :, 2]
+    n = torch.linalg.norm(v, dim=1)
+    normalise = bool(flags & 1)
+    ray = v / n[:, None] if normalise else v
+    d = None
+    if depth is None:
+        d_src = torch.ones(R, dtype=dtype)
+    else:
+        d = depth.detach().to(dtype).clone().requires_grad_(True)
+        q = A[:, :, 0] * (x * d)[:, None] + A[:, :, 1] * (y * d)[:, None] + A[:, :, 2] * d[:, None]
+        d_src = torch.linalg.norm(q, dim=1)
+        if not normalise and _wrong != "dsrc_no_norm_div":
+            d_src = d_src / n
+    view = torch.ones_like(ray) if flags & 2 else -ray
+    out = dict(cam=cam.detach(), ray=ray.detach(), view=view.detach(), ray_norm=n.detach(), d_src=d_src.detach(),
+               mask=torch.isfinite(d_src.detach()) & (d_src.detach() != 0))
+    if grads is not None:
+        vg = view.detach() if _wrong == "view_grad_dropped" else view
+        loss = torch.zeros((), dtype=dtype)
+        for name, t in (("g_cam", cam), ("g_ray", ray), ("g_view", vg), ("g_norm", n), ("g_dsrc", d_src)):
+            if grads.get(name) is not None:
+                loss = loss + (t * grads[name].to(dtype)).sum()
+        if loss.requires_grad:
+            loss.backward()
+        gp = torch.zeros_like(Mp) if Mp.grad is None else Mp.grad
+        out.update(gM=gp.sum(0), condM=gp.abs().sum(0),
+                   g_depth=None if d is None else (torch.zeros_like(d) if d.grad is None else d.grad))
+    return out
+
+
+def camera_rays_refs(M, pix, depth, flags, grads=None):
+    r64 = camera_rays_ref(M, pix, depth, flags, torch.float64, grads)
+    r32 = camera_rays_ref(M, pix, depth, flags, torch.float32, grads)
+    names = ["cam", "ray", "view", "ray_norm", "d_src"] + (["gM"] if grads is not None else []) + \
+        (["g_depth"] if grads is not None and depth is not None else [])
+    e32 = {}
+    for nme in names:
+        a, b = r32[nme].double(), r64[nme].double()
+        fin = torch.isfinite(b) & torch.isfinite(a)
+        e32[nme] = (a - b)[fin].abs().max().item() if bool(fin.any()) else 0.0
+    return r64, e32, r32
+
+
+# ---- the ray loss ---------------------------------------------------------------------------------------------
+def f32r(x: float) -> float:
+    """A Python float rounded to f32 (what a float argument of the C ABI receives)."""
+    return torch.tensor(x, dtype=torch.float32).item()
+
+
+LOSS_W_RGB, LOSS_W_DEPTH = f32r(1.0), f32r(0.04)
+LOSS_GO = dict(total=f32r(1.0), l_rgb=f32r(-0.7), l_depth=f32r(0.45), l2_mean=f32r(0.3))
+
+
+def ray_loss_inputs(R, n_depth, mask_kind, seed=0):
+    """rgb, gt [R][3] in [0, 1) with rgb == gt on every fifth element; dp, dg [n_depth] in [0, 5) with
+    dp == dg on every third ray; mask [n_depth] bool or None ("none": no mask, "all", "one": exactly one
+    valid ray, "zero": none valid)."""
+    gen = torch.Generator().manual_seed(700 + 13 * R + n_depth + seed)
+    rgb, gt = torch.rand(R, 3, generator=gen), torch.rand(R, 3, generator=gen)
+    rgb.view(-1)[::5] = gt.view(-1)[::5]
+    dp, dg = 5 * torch.rand(n_depth, generator=gen), 5 * torch.rand(n_depth, generator=gen)
+    dp[::3] = dg[::3]
+    mask = None
+    if mask_kind != "none":
+        mask = torch.zeros(n_depth, dtype=torch.bool)
+        if mask_kind == "all":
+            mask[:] = True
+        elif mask_kind == "one":
+            mask[n_depth - 1 if n_depth % 3 != 1 else n_depth // 2] = True
+    assert mask_kind in LOSS_MASKS
+    return dict(rgb=rgb, gt=gt, dp=dp, dg=dg, mask=mask)
+
+
+def ray_loss_ref(rgb, gt, dp, dg, mask, l1, w_rgb, w_depth, go, dtype, _wrong=None):
+    """nerf_ray_loss by its header: l_rgb = sum |e| (l1) or sum e^2 over rgb [R][3], divided by R;
+    l_depth = sum over the mask of |dp - dg| / max(count, 1); l2_mean = mean e^2; total = w_rgb l_rgb +
+    w_depth l_depth; and the gradients of sum_k go[k] out[k] (go: dict, a missing entry is absent) by
+    autograd.  dp None: no depth term.  sums: the three raw sums (their terms are non-negative, so they
+    are their own sums of |term|)."""
+    R = rgb.shape[0]
+    r = rgb.detach().to(dtype).clone().requires_grad_(True)
+    e = r - gt.to(dtype)
+    s2, s1 = (e * e).sum(), e.abs().sum()
+    l_rgb = (s1 if l1 else s2) / float(3 * R if _wrong == "div_3R" else R)
+    l2_mean = s2 / float(3 * R)
+    p = q = None
+    sd, cnt = torch.zeros((), dtype=dtype), 0.0
+    l_depth = torch.zeros((), dtype=dtype)
+    if dp is not None:
+        p = dp.detach().to(dtype).clone().requires_grad_(True)
+        q = dg.detach().to(dtype).clone().requires_grad_(True)
+        m = torch.ones(p.shape[0], dtype=torch.bool) if (mask is None or _wrong == "mask_ignored") else mask.bool()
+        sd = ((p - q).abs() * m).sum()
+        cnt = float(m.sum())
+        l_depth = sd / (cnt if _wrong == "cnt_unclamped" else max(cnt, 1.0))
+    total = w_rgb * l_rgb + w_depth * l_depth
+    out = dict(total=total, l_rgb=l_rgb, l_depth=l_depth, l2_mean=l2_mean)
+    loss = torch.zeros((), dtype=dtype)
+    for k, w in go.items():
+        if w is not None:
+            loss = loss + w * out[k]
+    if loss.requires_grad:
+        loss.backward()
+    z = lambda t: None if t is None else (torch.zeros_like(t) if t.grad is None else t.grad)      # noqa: E731
+    res = {k: v.detach() for k, v in out.items()}
+    res.update(cnt=cnt, g_rgb=z(r), g_dp=z(p), g_dg=z(q), s1=s1.detach(), s2=s2.detach(), sd=sd.detach())
+    return res
+
+
+def ray_loss_refs(inp, l1, go, with_depth=True):
+    a = (inp["rgb"], inp["gt"], inp["dp"] if with_depth else None, inp["dg"] if with_depth else None, inp["mask"], l1,
+         LOSS_W_RGB, LOSS_W_DEPTH, go)
+    r64, r32 = ray_loss_ref(*a, torch.float64), ray_loss_ref(*a, torch.float32)
+    return r64, _e32(r32, r64, ("g_rgb",) + (("g_dp", "g_dg") if with_depth else ())), r32
+
+
+def ray_loss_scalar_bars(r64, R, n_depth, l1):
+    """The derived bars of the four scalars: tree_ceiling(n, 1024) of the raw sum over its divisor (the
+    ceiling's four spare roundings cover forming a term -- e, e e or |e| -- and the division), and for
+    total the weighted bars plus three roundings of |total| (two products and a sum)."""
+    c3, cd = tree_ceiling(3 * R, 1024), tree_ceiling(max(n_depth, 1), 1024)
+    b_rgb = c3 * (r64["s1"] if l1 else r64["s2"]).item() / R
+    b_l2 = c3 * r64["s2"].item() / (3 * R)
+    b_dep = cd * r64["sd"].item() / max(r64["cnt"], 1.0)
+    b_tot = LOSS_W_RGB * b_rgb + LOSS_W_DEPTH * b_dep + 3 * U24 * abs(r64["total"].item())
+    return dict(total=b_tot, l_rgb=b_rgb, l_depth=b_dep, l2_mean=b_l2)
+
+
+# ---- Adam --------------------------------------------------------------------------------------------------------
+def adam_inputs(n, steps=3, seed=0):
+    """p [n] ~ N(0, 1) and `steps` gradients whose magnitudes spread over 1e-20 .. 1e4 with exact zeros;
+    the last three elements (the n % 4 tail) keep O(1) gradients."""
+    gen = torch.Generator().manual_seed(900 + n + seed)
+    p = torch.randn(n, generator=gen)
+    gs = []
+    for _ in range(steps):
+        g = torch.randn(n, generator=gen)
+        mag = torch.pow(10.0, torch.randint(-20, 5, (n,), generator=gen).float())
+        mag[-3:] = 1.0
+        g = g * mag
+        if n > 8:
+            g[torch.randint(0, n - 3, (max(1, n // 16),), generator=gen)] = 0.0
+        gs.append(g)
+    return p, gs
+
+
+def adam_ref(p, g_list, hyper, dtype, _wrong=None):
+    """torch.optim.Adam (amsgrad off, maximize off) written out, step by step from step 0:
+    g += wd p; m = lerp(m, g, 1 - b1); v = b2 v + (1 - b2) g g; p -= lr / (1 - b1^t) m / (sqrt(v) /
+    sqrt(1 - b2^t) + eps), the bias corrections in Python doubles -> (p, m, v).  hyper: dict(lr, b1, b2,
+    eps, wd) and optionally om2: the 1 - beta2 of slot 6 of the device block, which the kernel uses as given
+    whatever beta2 is (a block whose slot 6 is not exactly 1 - slot 3)."""
+    import math
+    lr, b1, b2, eps, wd = (hyper[k] for k in ("lr", "b1", "b2", "eps", "wd"))
+    p = p.detach().to(dtype).clone()
+    m, v = torch.zeros_like(p), torch.zeros_like(p)
+    n = p.numel()
+    live = n if _wrong != "tail_untouched" else n - n % 4
+    for t, g in enumerate(g_list, start=0 if _wrong == "step_not_advanced" else 1):
+        g = g.to(dtype)
+        pn, mn, vn = p.clone(), m.clone(), v.clone()
+        if wd != 0:
+            g = g + wd * pn
+        mn = mn + (g - mn) * (1 - b1)
+        vn = vn * b2 + hyper.get("om2", 1 - b2) * (g * g)
+        bc1, bc2 = 1 - b1 ** t, 1 - b2 ** t
+        if bc1 == 0:
+            return p * float("nan"), m, v
+        denom = vn.sqrt() / math.sqrt(bc2) + eps
+        pn = pn - (lr / bc1) * (mn / denom)
+        p[:live], m[:live], v[:live] = pn[:live], mn[:live], vn[:live]
+    return p, m, v
+
+
+def adam_refs(p, g_list, hyper):
+    r64, r32 = adam_ref(p, g_list, hyper, torch.float64), adam_ref(p, g_list, hyper, torch.float32)
+    return r64, [(a.double() - b).abs().max().item() for a, b in zip(r32, r64)], r32
+
+
+def adam_bar(ref, e_f32):
+    """4 E_f32 + 4 2^-24 max|ref|."""
+    return F32_MARGIN * e_f32 + 4 * U24 * ref.abs().max().item()
+
+
+# ---- the weight pack ---------------------------------------------------------------------------------------------
+def chain_perm_ref(c, _wrong=None):
+    """The chain order of nerf_pack_weights (include/nerf_hip.h): within each 32 columns, image column
+    8 g + i holds column 4 g + i for i < 4 and 16 + 4 g + i - 4 otherwise."""
+    base, q = c - c % 32, c % 32
+    g, i = q // 8, q % 8
+    src = 4 * g + i if i < 4 else 16 + 4 * g + i - 4
+    if _wrong == "halves_exchanged":
+        src = (src + 16) % 32
+    return base + src
+
+
+def chain_perm_index(n, perm_k, _wrong=None):
+    """Column index of an n-wide chain image: the first perm_k columns in chain order, the rest in place."""
+    return torch.tensor([chain_perm_ref(c, _wrong) if c < perm_k else c for c in range(n)], dtype=torch.long)
+
+
+def split3_ref(x):
+    """x -> (hi, mid, lo) bf16 words, each round-to-nearest-even (torch .bfloat16())."""
+    h = x.bfloat16()
+    r = x - h.float()
+    m = r.bfloat16()
+    lo = (r - m.float()).bfloat16()
+    return [t.view(torch.int16) for t in (h, m, lo)]
+
+
+def image_ref(mat):
+    """[N][K] f32 -> bf16x3 image [3][K/8][N][8] (nerf_pack_desc.dst_s layout)."""
+    N, K = mat.shape
+    return torch.stack([p.view(N, K // 8, 8).permute(1, 0, 2) for p in split3_ref(mat)])
+
+
+def pair_row_exp(mat):
+    """The row exponents of the fp16 pair form: e_r with max|row| 2^e_r in [2^14, 2^15); 0 for a zero
+    row; 140 for a subnormal row maximum (the largest scale an f32 exponent field gives: 2^140 times a
+    subnormal stays below 2^14)."""
+    rmax = mat.abs().amax(1).double()
+    e = 14 - torch.floor(torch.log2(rmax.clamp_min(1e-300))).long()
+    return torch.where(rmax > 0, e.clamp_max(140), torch.zeros_like(e))
+
+
+def pair_image_ref(mat, perm=None, compact=False):
+    """The fp16 pair image of a padded [N][K] f32 matrix (include/nerf_hip.h, mode 2): image column c
+    holds matrix column perm[c] (None: c); hi = fp16(x 2^e), lo = fp16(x 2^e - hi), both round to
+    nearest even -> dict(hi, lo: int16 [K/8][N][8]; e: int32 [N], the word at plane 2 chunk 0 of each
+    row; with compact also ce, the int32 [N] array at chunk 1)."""
+    N, K = mat.shape
+    m = mat if perm is None else mat[:, perm]
+    e = pair_row_exp(m)
+    xs = (m.double() * torch.pow(2.0, e.double()).unsqueeze(1)).float()      # exact: a power of two (2^140 needs fp64)
+    h = xs.half()
+    lo = (xs - h.float()).half()
+    lay = lambda t: t.view(torch.int16).view(N, K // 8, 8).permute(1, 0, 2).contiguous()      # noqa: E731
+    out = dict(hi=lay(h), lo=lay(lo), e=e.to(torch.int32))
+    if compact:
+        out["ce"] = e.to(torch.int32)
+    return out
+
+
+def pair_image_read(img, compact=False):
+    """The same fields out of a device image [3][K/8][N][8] int16."""
+    img = img.detach().cpu()
+    N = img.shape[2]
+    out = dict(hi=img[0].contiguous(), lo=img[1].contiguous(),
+               e=img[2, 0, :, 0:2].contiguous().view(torch.int32).view(N))
+    if compact:
+        out["ce"] = img[2, 1].contiguous().view(-1)[:2 * N].view(torch.int32)
+    return out
+
+
+def pair_image_value(fields):
+    """(hi + lo) 2^-e, [N][K] fp64."""
+    h, lo = (fields[k].permute(1, 0, 2).reshape(fields[k].shape[1], -1).view(torch.float16).double() for k in ("hi", "lo"))
+    return (h + lo) * torch.pow(2.0, -fields["e"].double()).unsqueeze(1)
+
+
+def pack_edge_rows(W):
+    """Edge rows into a weight [rows][cols] (rows >= 8): row 1 zero, row 2 with maximum exactly 2^-3, row
+    3 subnormal, row 4 with maximum 3e38 -> W."""
+    W = W.clone()
+    W[1] = 0.0
+    W[2] = W[2] / W[2].abs().max() * 0.125
+    W[3] = W[3] / W[3].abs().max() * 1e-39
+    W[4] = W[4] / W[4].abs().max() * 3e38
+    return W

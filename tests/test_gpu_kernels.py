@@ -10,6 +10,7 @@ import torch
 
 from model import _hip
 from oracle import nerf_oracle as orc
+from tests.helpers import image_ref as _image_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -436,21 +437,6 @@ def test_split_accuracy_weight_gradient(dev, spread):
     tiny = 4 * 2.0 ** -24
     assert errs[1] <= 1.5 * errs[0] + tiny, errs
     assert errs[2] <= 1.5 * errs[0] + tiny, errs
-
-
-def _split3_ref(x):
-    """x -> (hi, mid, lo) bf16 words, each round-to-nearest-even (torch .bfloat16())."""
-    h = x.bfloat16()
-    r = x - h.float()
-    m = r.bfloat16()
-    lo = (r - m.float()).bfloat16()
-    return [t.view(torch.int16) for t in (h, m, lo)]
-
-
-def _image_ref(mat):
-    """[N][K] f32 -> bf16x3 image [3][K/8][N][8] (nerf_pack_desc.dst_s layout)."""
-    N, K = mat.shape
-    return torch.stack([p.view(N, K // 8, 8).permute(1, 0, 2) for p in _split3_ref(mat)])
 
 
 def test_pack_split_images(dev):

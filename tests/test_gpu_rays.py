@@ -212,7 +212,7 @@ def test_camera_rays_match_oracle(dev, normalise):
     assert torch.equal(m.cpu(), m_r)
     assert torch.equal(view.cpu(), -ray.cpu())
     _, _, view1, _, ds1, _ = rays.camera_rays_hip(M, b["pixels"].to(dev), None, normalise, view_ones=True)
-    assert bool((view1 == 1).all()) and (bool((ds1 == 1).all()) if normalise else True)
+    assert bool((view1 == 1).all()) and bool((ds1 == 1).all())      # no depth: d_src = 1 under either flag
 
 
 @pytest.mark.parametrize("normalise", [True, False])
