@@ -44,7 +44,8 @@ extern "C" {
  * wt_cimg) and torch-exact Adam, 14 nerf_linear_bwd_weight_jobs and nerf_pair_backward's 12P gXY,
  * 15 the chain images' compact exponent arrays (nerf_pack_desc dst_cs / dst_cts) and
  * nerf_linear_bwd_weight_job_groups.  Additive within 15 (no existing signature changed): the
- * frozen-field entries and nerf_image_metrics(_workspace_bytes). */
+ * frozen-field entries, nerf_image_metrics(_workspace_bytes) and nerf_pair_forward_ssim /
+ * nerf_pair_backward_ssim. */
 #define NERF_HIP_ABI_VERSION 15
 int nerf_hip_abi_version(void);
 const char* nerf_hip_last_error(void);
@@ -676,6 +677,26 @@ int nerf_pair_backward(const float* d1, const float* d2, int h, int w, const flo
                        const float* work, const int* nn, const float* out3, const float* go_pc,
                        const float* go_rgbs, float* gXY, float* g_d1, float* g_d2, float* g13, float* part13,
                        void* stream);
+/* The same pair with training.with_ssim (losses.py:152-159 with the SSIM of :232-263; the chamfer
+ * term, X, Y and nn are those of nerf_pair_forward, bit for bit):
+ *   loss_rgb_s = mean over valid elements of 0.15 clamp(|rgb1 - rgb2|, 0, 1) + 0.85 SSIM(rgb1, rgb2),
+ * rgb1 = img1(p), rgb2 = img2(proj(R pc1 + t)) as (1, h, w, 3) tensors, which the NCHW SSIM module reads
+ * as C = row, H = column, W = colour: the 3 x 3 mean window of (row, column c, colour k) covers columns
+ * c-1 .. c+1 of the same row and colours k-1 .. k+1, both reflected without repeating the edge
+ * (ReflectionPad2d(1)); C1 = 0.01^2, C2 = 0.03^2, clamp((1 - n / d) / 2, 0, 1).  The mask is the
+ * output's: a window reads its neighbours' samples whatever their validity, so the backward gives
+ * geometry gradient to every unclamped point with a valid point within one column of its row.
+ * samples: [2][P][3] floats, written by the forward (every point's rgb1, then rgb2) and read by the
+ * backward.  img1 / img2 and samples are required (NERF_EINVAL without); one launch more than
+ * nerf_pair_forward, none more than nerf_pair_backward, no atomics added. */
+int nerf_pair_forward_ssim(const float* d1, const float* d2, int h, int w, const float* K, const float* Rt,
+                           const float* s1, float nl, const float* img1, const float* img2, float* work,
+                           int* nn, float* samples, float* out3, void* stream);
+int nerf_pair_backward_ssim(const float* d1, const float* d2, int h, int w, const float* K, const float* Rt,
+                            const float* s1, float nl, const float* img1, const float* img2,
+                            int rgbs_detach_scale, const float* work, const int* nn, const float* samples,
+                            const float* out3, const float* go_pc, const float* go_rgbs, float* gXY,
+                            float* g_d1, float* g_d2, float* g13, float* part13, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Windowed image metrics of the novel-view evaluation (metrics.hip; model/eval_images.py:94-97:

@@ -14,6 +14,11 @@
 //             k_pair_bwd_reduce.
 // Sizes are tiny (47 x 155 = 7285 points at V_KITTI): the budget is launches, and the NN
 // search (2 x 53 M pair distances) is spread over ~2000 workgroups instead of 29.
+//
+// with_ssim (losses.py:152-159 with SSIM, :232-263): the per-point kernel keeps every point's
+// img1 / img2 samples, k_pair_ssim (one more launch forward) forms the 3 x 3 windows and the
+// blended partials from them, and the backward's per-point kernel gathers d rgb_s / d sample
+// from the saved samples of columns c-2 .. c+2 of its row (no launch more, no atomics).
 #include "common.hpp"
 #include "mat4.hpp"
 
@@ -115,10 +120,177 @@ __device__ __forceinline__ Reproj reproject(const PairArgs& a, const PairConst& 
 
 constexpr int PT = 256;   // threads per point-kernel workgroup
 
+// the workgroup's {sum, count} of the rgb_s term, waves added in order
+__device__ __forceinline__ void pair_block_partials(float s, float n, float (*red)[2], float* __restrict__ rgbs_part) {
+    s = wave_sum(s);
+    n = wave_sum(n);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = s; red[threadIdx.x >> 6][1] = n; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float ss = 0.f, nn = 0.f;
+        for (int wv = 0; wv < PT / 64; ++wv) { ss += red[wv][0]; nn += red[wv][1]; }
+        rgbs_part[2 * blockIdx.x] = ss;
+        rgbs_part[2 * blockIdx.x + 1] = nn;
+    }
+}
+
+// ---------------------------------------------------------------------------- with_ssim
+// bilinear() of a point that need not be valid: a projection a whole pixel or more outside
+// the image (or not finite) samples the zero padding only: value and derivative 0
+__device__ __forceinline__ float bilinear_pad(const float* __restrict__ plane, int h, int w, float px, float py,
+                                              float* dpx = nullptr, float* dpy = nullptr) {
+#pragma clang fp contract(off)
+    const float ix = (px + 1.f) * 0.5f * (float)(w - 1);
+    const float iy = (py + 1.f) * 0.5f * (float)(h - 1);
+    if (!(ix > -1.f && ix < (float)w && iy > -1.f && iy < (float)h)) {
+        if (dpx) { *dpx = 0.f; *dpy = 0.f; }
+        return 0.f;
+    }
+    return bilinear(plane, h, w, px, py, dpx, dpy);
+}
+
+// validity of point idx, by the geometry of k_pair_points (the same bits)
+__device__ __forceinline__ bool pair_point_valid(const PairArgs& a, const PairConst& m, int idx) {
+    float x, y, pc1[3];
+    pc_pixel(idx, a.h, a.w, x, y);
+    unproject_pt(m.Kinv, x, y, a.d1[idx], pc1);
+    return reproject(a, m, pc1).valid;
+}
+
+// SSIM(rgb1, rgb2) of losses.py:232-263 on the (B, h, w, 3) tensors the trainer passes: N = B,
+// C = image row, H = image column, W = colour.  The 3 x 3 window of (row, column c, colour k)
+// covers columns c-1 .. c+1 of the same row and colours k-1 .. k+1, both reflected without
+// repeating the edge (column -1 -> 1, w -> w-2; colour -1 -> 1, 3 -> 1); rows never mix.
+__device__ __forceinline__ int ssim_reflect(int t, int w) { return t < 0 ? -t : (t >= w ? 2 * (w - 1) - t : t); }
+// how often colour k enters the window of colour k'
+__device__ __forceinline__ int ssim_cw(int kp, int k) {
+    return (k == kp) + (k == (kp == 0 ? 1 : kp - 1)) + (k == (kp == 2 ? 1 : kp + 1));
+}
+
+// the window moments of output column j of the row at `base`, all three colours, in fp64
+// (sigma^2 = E[x^2] - mu^2 cancels against C2 = 9e-4 in f32): E[x], E[y], E[x^2], E[y^2], E[xy]
+struct SsimWin { double mx[3], my[3], xx[3], yy[3], xy[3]; };
+__device__ __forceinline__ SsimWin ssim_window(const float* __restrict__ samp, int P, int base, int w, int j) {
+    SsimWin W;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) W.mx[k] = W.my[k] = W.xx[k] = W.yy[k] = W.xy[k] = 0.0;
+#pragma unroll
+    for (int dj = -1; dj <= 1; ++dj) {
+        const int q = base + ssim_reflect(j + dj, w);
+        double x[3], y[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { x[k] = (double)samp[3 * q + k]; y[k] = (double)samp[3 * (P + q) + k]; }
+#pragma unroll
+        for (int kp = 0; kp < 3; ++kp) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double m = (double)ssim_cw(kp, k);
+                W.mx[kp] += m * x[k]; W.my[kp] += m * y[k];
+                W.xx[kp] += m * x[k] * x[k]; W.yy[kp] += m * y[k] * y[k]; W.xy[kp] += m * x[k] * y[k];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        W.mx[k] /= 9.0; W.my[k] /= 9.0; W.xx[k] /= 9.0; W.yy[k] /= 9.0; W.xy[k] /= 9.0;
+    }
+    return W;
+}
+
+// n and d of the quotient of window colour kp
+struct SsimQ { double A1, A2, B1, B2, n, d, raw; };
+__device__ __forceinline__ SsimQ ssim_quotient(const SsimWin& W, int kp) {
+    constexpr double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
+    SsimQ q;
+    const double sx = W.xx[kp] - W.mx[kp] * W.mx[kp], sy = W.yy[kp] - W.my[kp] * W.my[kp];
+    const double sxy = W.xy[kp] - W.mx[kp] * W.my[kp];
+    q.A1 = 2.0 * W.mx[kp] * W.my[kp] + C1;
+    q.A2 = 2.0 * sxy + C2;
+    q.B1 = W.mx[kp] * W.mx[kp] + W.my[kp] * W.my[kp] + C1;
+    q.B2 = sx + sy + C2;
+    q.n = q.A1 * q.A2;
+    q.d = q.B1 * q.B2;
+    q.raw = (1.0 - q.n / q.d) * 0.5;     // before clamp(., 0, 1)
+    return q;
+}
+
+// forward: the blended term 0.15 clamp(|rgb1 - rgb2|, 0, 1) + 0.85 SSIM of the valid points from
+// the saved samples -> the {sum, count} partials of k_pair_points
+__global__ __launch_bounds__(PT) void k_pair_ssim(PairArgs a, const float* __restrict__ samp,
+                                                  float* __restrict__ rgbs_part) {
+    __shared__ float red[PT / 64][2];
+    const int i = blockIdx.x * PT + threadIdx.x;
+    float s = 0.f, n = 0.f;
+    if (i < a.P) {
+        PairConst m;
+        m.load(a);
+        if (pair_point_valid(a, m, i)) {
+            const int row = i / a.w, col = i - row * a.w;
+            const SsimWin W = ssim_window(samp, a.P, row * a.w, a.w, col);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double map = fmin(fmax(ssim_quotient(W, k).raw, 0.0), 1.0);
+                const float ad = fminf(fmaxf(fabsf(samp[3 * i + k] - samp[3 * (a.P + i) + k]), 0.f), 1.f);
+                s += (float)(0.15 * (double)ad + 0.85 * map);
+            }
+            n = 3.f;
+        }
+    }
+    pair_block_partials(s, n, red, rgbs_part);
+}
+
+// backward: d(sum over valid outputs of the blended term) / d rgb2[i][k], k = 0..2, times g, in
+// gather form: the outputs whose window holds (i, k) are columns c-1 .. c+1 of i's row and the
+// colours k' next to k, each with the multiplicity the reflection gives it; the mask is the
+// output's, so an invalid i collects from valid neighbours
+__device__ __forceinline__ void ssim_grad_rgb2(const PairArgs& a, const PairConst& m, const float* __restrict__ samp,
+                                               int i, bool valid_i, float g, float gv[3]) {
+    const int P = a.P, w = a.w;
+    const int row = i / w, c = i - row * w, base = row * w;
+    double x[3], y[3], acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { x[k] = (double)samp[3 * i + k]; y[k] = (double)samp[3 * (P + i) + k]; }
+    for (int dj = -1; dj <= 1; ++dj) {
+        const int j = c + dj;
+        if (j < 0 || j >= w) continue;
+        if (!(dj == 0 ? valid_i : pair_point_valid(a, m, base + j))) continue;
+        const int mult = (ssim_reflect(j - 1, w) == c) + (j == c) + (ssim_reflect(j + 1, w) == c);
+        const SsimWin W = ssim_window(samp, P, base, w, j);
+#pragma unroll
+        for (int kp = 0; kp < 3; ++kp) {
+            const SsimQ q = ssim_quotient(W, kp);
+            if (!(q.raw >= 0.0 && q.raw <= 1.0)) continue;      // clamp(., 0, 1) passes the gradient on [0, 1]
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int cw = ssim_cw(kp, k);
+                if (cw == 0) continue;
+                // one tap of value (x, y): d mu_y = 1/9, d sigma_y^2 = 2 (y - mu_y) / 9, d sigma_xy = (x - mu_x) / 9
+                const double dn = (2.0 * W.mx[kp] * q.A2 + q.A1 * 2.0 * (x[k] - W.mx[kp])) / 9.0;
+                const double dd = (2.0 * W.my[kp] * q.B2 + q.B1 * 2.0 * (y[k] - W.my[kp])) / 9.0;
+                acc[k] += (double)(mult * cw) * (-(dn * q.d - q.n * dd) / (2.0 * q.d * q.d));
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        double ab = 0.0;
+        if (valid_i) {
+            // abs' = sign (0 at 0); clamp(., 0, 1) passes the gradient on [0, 1]
+            const double e = x[k] - y[k];
+            ab = fabs(e) <= 1.0 ? -(e > 0.0 ? 1.0 : (e < 0.0 ? -1.0 : 0.0)) : 0.0;
+        }
+        gv[k] = (float)((double)g * (0.85 * acc[k] + 0.15 * ab));
+    }
+}
+
 // forward per point: X, Y and the rgb_s partial sums (sum of clamped |diff| over valid
 // points and channels, number of valid elements) per workgroup
+// SSIM: every point's samples go to samp ([2][P][3]: img1 at the pixel, img2 at the reprojection,
+// whatever the point's validity: the windows of its neighbours read them) and the partials are
+// left to k_pair_ssim
+template <bool SSIM>
 __global__ __launch_bounds__(PT) void k_pair_points(PairArgs a, float* __restrict__ X, float* __restrict__ Y,
-                                                    float* __restrict__ rgbs_part) {
+                                                    float* __restrict__ rgbs_part, float* __restrict__ samp) {
 #pragma clang fp contract(off)
     __shared__ float red[PT / 64][2];
     const int i = blockIdx.x * PT + threadIdx.x;
@@ -130,7 +302,15 @@ __global__ __launch_bounds__(PT) void k_pair_points(PairArgs a, float* __restric
         pc_pixel(i, a.h, a.w, x, y);
         unproject_pt(m.Kinv, x, y, a.d1[i], pc1);
         unproject_pt(m.Kinv, x, y, a.d2[i], pc2);
-        if (a.img1 != nullptr) {
+        if constexpr (SSIM) {
+            const Reproj r = reproject(a, m, pc1);
+            const int hw = a.h * a.w;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                samp[3 * i + c] = bilinear(a.img1 + c * hw, a.h, a.w, x, y);
+                samp[3 * (a.P + i) + c] = bilinear_pad(a.img2 + c * hw, a.h, a.w, r.px, r.py);
+            }
+        } else if (a.img1 != nullptr) {
             const Reproj r = reproject(a, m, pc1);
             if (r.valid) {
                 const int hw = a.h * a.w;
@@ -154,16 +334,8 @@ __global__ __launch_bounds__(PT) void k_pair_points(PairArgs a, float* __restric
             Y[3 * i + k] = pc2[k];
         }
     }
-    s = wave_sum(s);
-    n = wave_sum(n);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = s; red[threadIdx.x >> 6][1] = n; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float ss = 0.f, nn = 0.f;
-        for (int wv = 0; wv < PT / 64; ++wv) { ss += red[wv][0]; nn += red[wv][1]; }
-        rgbs_part[2 * blockIdx.x] = ss;
-        rgbs_part[2 * blockIdx.x + 1] = nn;
-    }
+    if constexpr (SSIM) return;
+    pair_block_partials(s, n, red, rgbs_part);
 }
 
 // chamfer nearest neighbours, both directions (blockIdx.z: 0 = X -> Y, 1 = Y -> X), the
@@ -312,6 +484,9 @@ __device__ __forceinline__ float pair_scattered(const unsigned long long* s, int
 // per point: the direct chamfer terms plus the scattered ones -> dX_i, dY_i; the rgb_s term
 // -> d pc1_rot; then d1 / d2 gradients and the R, t, scale partials of the workgroup
 // (part[block][13] = {R (9), t (3), s1})
+// SSIM: the rgb_s term is the with_ssim one, its gradient gathered from the saved samples `samp`;
+// every unclamped point takes part, valid or not
+template <bool SSIM>
 __global__ __launch_bounds__(PT) void k_pair_bwd_points(PairArgs a, const float* __restrict__ X,
                                                         const float* __restrict__ Y, const int* __restrict__ nn,
                                                         const float* __restrict__ go_pc,
@@ -320,7 +495,7 @@ __global__ __launch_bounds__(PT) void k_pair_bwd_points(PairArgs a, const float*
                                                         const unsigned long long* __restrict__ gX,
                                                         const unsigned long long* __restrict__ gY,
                                                         float* __restrict__ g_d1, float* __restrict__ g_d2,
-                                                        float* __restrict__ part) {
+                                                        float* __restrict__ part, const float* __restrict__ samp) {
     __shared__ float red[PT / 64][13];
     const int i = blockIdx.x * PT + threadIdx.x;
     const int P = a.P;
@@ -386,10 +561,21 @@ __global__ __launch_bounds__(PT) void k_pair_bwd_points(PairArgs a, const float*
         // rgb_s: d/d(v2_c) of clamp(|v1_c - v2_c|, 0, 1) / N  (N valid elements)
         if (a.img1 != nullptr && go_rgbs != nullptr && red_out[2] > 0.f) {
             const Reproj r = reproject(a, m, pc1);
-            if (r.valid && !r.bad) {
+            if ((SSIM || r.valid) && !r.bad) {
                 const int hw = a.h * a.w;
                 const float g = *go_rgbs / red_out[2];
                 float gpx = 0.f, gpy = 0.f;
+                if constexpr (SSIM) {
+                    float gv[3];
+                    ssim_grad_rgb2(a, m, samp, i, r.valid, g, gv);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        float dpx, dpy;
+                        bilinear_pad(a.img2 + c * hw, a.h, a.w, r.px, r.py, &dpx, &dpy);
+                        gpx += gv[c] * dpx;
+                        gpy += gv[c] * dpy;
+                    }
+                } else {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const float v1 = bilinear(a.img1 + c * hw, a.h, a.w, x, y);
@@ -401,6 +587,7 @@ __global__ __launch_bounds__(PT) void k_pair_bwd_points(PairArgs a, const float*
                     const float gv2 = (ae <= 1.f) ? -g * (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) : 0.f;
                     gpx += gv2 * dpx;
                     gpy += gv2 * dpy;
+                }
                 }
                 // p = h3[:2] / h3[2]
                 const float iz = 1.f / r.h3[2];
@@ -484,13 +671,17 @@ extern "C" int nerf_pair_workspace(int n_points, int* n_chunks, int64_t* floats)
     return NERF_OK;
 }
 
-extern "C" int nerf_pair_forward(const float* d1, const float* d2, int h, int w, const float* K16,
-                                 const float* Rt16, const float* s1, float nl, const float* img1,
-                                 const float* img2, float* work, int* nn, float* out3, void* stream) {
+static int pair_forward_impl(const char* fn, const float* d1, const float* d2, int h, int w, const float* K16,
+                             const float* Rt16, const float* s1, float nl, const float* img1, const float* img2,
+                             float* work, int* nn, float* samples, bool ssim, float* out3, void* stream) {
     PairArgs a;
     const int rc = fill_args(a, d1, d2, h, w, K16, Rt16, s1, nl, img1, img2, 0);
     if (rc != NERF_OK) return rc;
     NERF_CHECK_PTR(work); NERF_CHECK_PTR(nn); NERF_CHECK_PTR(out3);
+    if (ssim) {
+        NERF_CHECK(img1 != nullptr, "%s: the SSIM term needs img1 and img2", fn);
+        NERF_CHECK(samples != nullptr, "%s: samples is NULL ([2][P][3] floats)", fn);
+    }
     const int P = a.P;
     int nc = 1;
     nerf_pair_workspace(P, &nc, nullptr);
@@ -501,12 +692,64 @@ extern "C" int nerf_pair_forward(const float* d1, const float* d2, int h, int w,
     float* rgbs_part = reinterpret_cast<float*>(part + 2 * (size_t)nc * P);
     float* dist_part = rgbs_part + 2 * nb;
     hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(k_pair_points, dim3(nb), dim3(PT), 0, s, a, X, Y, rgbs_part);
+    if (ssim) hipLaunchKernelGGL(k_pair_points<true>, dim3(nb), dim3(PT), 0, s, a, X, Y, rgbs_part, samples);
+    else hipLaunchKernelGGL(k_pair_points<false>, dim3(nb), dim3(PT), 0, s, a, X, Y, rgbs_part, (float*)nullptr);
     const int chunk = ((P + nc - 1) / nc + NN_T - 1) / NN_T * NN_T;
     hipLaunchKernelGGL(k_nn_part, dim3((P + NN_T - 1) / NN_T, nc, 2), dim3(NN_T), 0, s, X, Y, P, chunk, part);
     hipLaunchKernelGGL(k_nn_final, dim3(nb), dim3(PT), 0, s, X, Y, P, nc, part, nn, dist_part);
+    if (ssim) hipLaunchKernelGGL(k_pair_ssim, dim3(nb), dim3(PT), 0, s, a, (const float*)samples, rgbs_part);
     hipLaunchKernelGGL(k_pair_reduce, dim3(1), dim3(256), 0, s, dist_part, img1 ? rgbs_part : nullptr, nb, P, out3);
-    return check_launch(__func__);
+    return check_launch(fn);
+}
+
+extern "C" int nerf_pair_forward(const float* d1, const float* d2, int h, int w, const float* K16,
+                                 const float* Rt16, const float* s1, float nl, const float* img1,
+                                 const float* img2, float* work, int* nn, float* out3, void* stream) {
+    return pair_forward_impl(__func__, d1, d2, h, w, K16, Rt16, s1, nl, img1, img2, work, nn, nullptr, false, out3,
+                             stream);
+}
+
+extern "C" int nerf_pair_forward_ssim(const float* d1, const float* d2, int h, int w, const float* K16,
+                                      const float* Rt16, const float* s1, float nl, const float* img1,
+                                      const float* img2, float* work, int* nn, float* samples, float* out3,
+                                      void* stream) {
+    return pair_forward_impl(__func__, d1, d2, h, w, K16, Rt16, s1, nl, img1, img2, work, nn, samples, true, out3,
+                             stream);
+}
+
+static int pair_backward_impl(const char* fn, const float* d1, const float* d2, int h, int w, const float* K16,
+                              const float* Rt16, const float* s1, float nl, const float* img1, const float* img2,
+                              int rgbs_detach_scale, const float* work, const int* nn, const float* samples, bool ssim,
+                              const float* out3, const float* go_pc, const float* go_rgbs, float* gXY, float* g_d1,
+                              float* g_d2, float* g13, float* part13, void* stream) {
+    PairArgs a;
+    const int rc = fill_args(a, d1, d2, h, w, K16, Rt16, s1, nl, img1, img2, rgbs_detach_scale);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_PTR(work); NERF_CHECK_PTR(nn); NERF_CHECK_PTR(out3); NERF_CHECK_PTR(gXY); NERF_CHECK_PTR(g13);
+    NERF_CHECK_PTR(part13);
+    if (ssim) {
+        NERF_CHECK(img1 != nullptr, "%s: the SSIM term needs img1 and img2", fn);
+        NERF_CHECK(samples != nullptr, "%s: samples is NULL ([2][P][3] floats)", fn);
+    }
+    const int P = a.P;
+    const int nb = (P + PT - 1) / PT;
+    const float* X = work;
+    const float* Y = X + 3 * (size_t)P;
+    NERF_CHECK(((uintptr_t)gXY & 7u) == 0, "%s: gXY must be 8-byte aligned (64-bit fixed-point sums)", fn);
+    unsigned long long* gX = reinterpret_cast<unsigned long long*>(gXY);
+    unsigned long long* gY = gX + 3 * (size_t)P;
+    hipStream_t s = as_stream(stream);
+    (void)hipMemsetAsync(gXY, 0, 6 * (size_t)P * sizeof(unsigned long long), s);
+    if (go_pc != nullptr) hipLaunchKernelGGL(k_pair_bwd_scatter, dim3(nb), dim3(PT), 0, s, X, Y, P, nn, gX, gY);
+    if (ssim)
+        hipLaunchKernelGGL(k_pair_bwd_points<true>, dim3(nb), dim3(PT), 0, s, a, X, Y, nn, go_pc, go_rgbs, out3,
+                           (const unsigned long long*)gX, (const unsigned long long*)gY, g_d1, g_d2, part13, samples);
+    else
+        hipLaunchKernelGGL(k_pair_bwd_points<false>, dim3(nb), dim3(PT), 0, s, a, X, Y, nn, go_pc, go_rgbs, out3,
+                           (const unsigned long long*)gX, (const unsigned long long*)gY, g_d1, g_d2, part13,
+                           (const float*)nullptr);
+    hipLaunchKernelGGL(k_pair_bwd_reduce, dim3(1), dim3(64), 0, s, (const float*)part13, nb, g13);
+    return check_launch(fn);
 }
 
 extern "C" int nerf_pair_backward(const float* d1, const float* d2, int h, int w, const float* K16,
@@ -514,23 +757,16 @@ extern "C" int nerf_pair_backward(const float* d1, const float* d2, int h, int w
                                   const float* img2, int rgbs_detach_scale, const float* work, const int* nn,
                                   const float* out3, const float* go_pc, const float* go_rgbs, float* gXY,
                                   float* g_d1, float* g_d2, float* g13, float* part13, void* stream) {
-    PairArgs a;
-    const int rc = fill_args(a, d1, d2, h, w, K16, Rt16, s1, nl, img1, img2, rgbs_detach_scale);
-    if (rc != NERF_OK) return rc;
-    NERF_CHECK_PTR(work); NERF_CHECK_PTR(nn); NERF_CHECK_PTR(out3); NERF_CHECK_PTR(gXY); NERF_CHECK_PTR(g13);
-    NERF_CHECK_PTR(part13);
-    const int P = a.P;
-    const int nb = (P + PT - 1) / PT;
-    const float* X = work;
-    const float* Y = X + 3 * (size_t)P;
-    NERF_CHECK(((uintptr_t)gXY & 7u) == 0, "%s: gXY must be 8-byte aligned (64-bit fixed-point sums)", __func__);
-    unsigned long long* gX = reinterpret_cast<unsigned long long*>(gXY);
-    unsigned long long* gY = gX + 3 * (size_t)P;
-    hipStream_t s = as_stream(stream);
-    (void)hipMemsetAsync(gXY, 0, 6 * (size_t)P * sizeof(unsigned long long), s);
-    if (go_pc != nullptr) hipLaunchKernelGGL(k_pair_bwd_scatter, dim3(nb), dim3(PT), 0, s, X, Y, P, nn, gX, gY);
-    hipLaunchKernelGGL(k_pair_bwd_points, dim3(nb), dim3(PT), 0, s, a, X, Y, nn, go_pc, go_rgbs, out3,
-                       (const unsigned long long*)gX, (const unsigned long long*)gY, g_d1, g_d2, part13);
-    hipLaunchKernelGGL(k_pair_bwd_reduce, dim3(1), dim3(64), 0, s, (const float*)part13, nb, g13);
-    return check_launch(__func__);
+    return pair_backward_impl(__func__, d1, d2, h, w, K16, Rt16, s1, nl, img1, img2, rgbs_detach_scale, work, nn, nullptr,
+                              false, out3, go_pc, go_rgbs, gXY, g_d1, g_d2, g13, part13, stream);
+}
+
+extern "C" int nerf_pair_backward_ssim(const float* d1, const float* d2, int h, int w, const float* K16,
+                                       const float* Rt16, const float* s1, float nl, const float* img1,
+                                       const float* img2, int rgbs_detach_scale, const float* work, const int* nn,
+                                       const float* samples, const float* out3, const float* go_pc,
+                                       const float* go_rgbs, float* gXY, float* g_d1, float* g_d2, float* g13,
+                                       float* part13, void* stream) {
+    return pair_backward_impl(__func__, d1, d2, h, w, K16, Rt16, s1, nl, img1, img2, rgbs_detach_scale, work, nn, samples,
+                              true, out3, go_pc, go_rgbs, gXY, g_d1, g_d2, g13, part13, stream);
 }

@@ -172,6 +172,10 @@ _SIGS = {
     "nerf_pair_forward": ([_c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_pair_backward": ([_c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p,
                             _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_pair_forward_ssim": ([_c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                _c_p], _c_i),
+    "nerf_pair_backward_ssim": ([_c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p,
+                                 _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_image_metrics_workspace_bytes": ([_c_i, _c_i, _c_i, _c_i], ctypes.c_size_t),
     "nerf_image_metrics": ([_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i, _c_i,
                             _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p], _c_i),
@@ -588,6 +592,19 @@ def pair_backward(d1, d2, h, w, K, Rt, s1, nl, img1, img2, rgbs_detach_scale, wo
     _call("nerf_pair_backward", _ptr(d1), _ptr(d2), int(h), int(w), _ptr(K), _ptr(Rt), _ptr(s1), float(nl),
           _ptr(img1), _ptr(img2), int(rgbs_detach_scale), _ptr(work), _ptr(nn), _ptr(out3), _ptr(go_pc),
           _ptr(go_rgbs), _ptr(gxy), _ptr(g_d1), _ptr(g_d2), _ptr(g13), _ptr(part13), _stream())
+
+
+def pair_forward_ssim(d1, d2, h, w, K, Rt, s1, nl, img1, img2, work, nn, samples, out3):
+    """nerf_pair_forward with the with_ssim reprojection term; samples: [2][P][3] floats, kept for the backward."""
+    _call("nerf_pair_forward_ssim", _ptr(d1), _ptr(d2), int(h), int(w), _ptr(K), _ptr(Rt), _ptr(s1), float(nl),
+          _ptr(img1), _ptr(img2), _ptr(work), _ptr(nn), _ptr(samples), _ptr(out3), _stream())
+
+
+def pair_backward_ssim(d1, d2, h, w, K, Rt, s1, nl, img1, img2, rgbs_detach_scale, work, nn, samples, out3, go_pc,
+                       go_rgbs, gxy, g_d1, g_d2, g13, part13):
+    _call("nerf_pair_backward_ssim", _ptr(d1), _ptr(d2), int(h), int(w), _ptr(K), _ptr(Rt), _ptr(s1), float(nl),
+          _ptr(img1), _ptr(img2), int(rgbs_detach_scale), _ptr(work), _ptr(nn), _ptr(samples), _ptr(out3),
+          _ptr(go_pc), _ptr(go_rgbs), _ptr(gxy), _ptr(g_d1), _ptr(g_d2), _ptr(g13), _ptr(part13), _stream())
 
 
 def image_metrics_workspace_bytes(batch, channels, height, width) -> int:

@@ -1,7 +1,12 @@
 """Image-pair terms of the full NoPe-NeRF step on the HIP kernels of pair.hip (SURVEY.md
 section 8(f) row 3): point clouds of both depth maps, relative pose, dense chamfer loss and
 reprojection (rgb_s) loss in four launches forward and four backward, replacing the ~200
-ATen launches of training.py:359-405 + losses.py:116-159.
+ATen launches of training.py:359-405 + losses.py:116-159.  With ``with_ssim`` the reprojection
+term is 0.15 clamp(|rgb1 - rgb2|, 0, 1) + 0.85 SSIM(rgb1, rgb2) (losses.py:152-159, 232-263) on
+nerf_pair_forward_ssim / nerf_pair_backward_ssim: one launch more forward, none more backward.
+The SSIM module reads the (B, h, w, 3) samples as NCHW, so its 3 x 3 window runs over three
+columns of one image row and the three colours, both reflected at their ends; the mask is the
+output's, so a point that projects outside the frame still gets gradient from valid neighbours.
 
 ``pair_losses`` keeps the reference inputs (depth maps at the pc resolution after the
 ``nearest_limit`` clamp, camera matrix, Rt_rel_12, scale1, the bilinearly resized images)
@@ -18,7 +23,7 @@ from . import _hip
 
 class _PairTerms(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, d1, d2, K, Rt, s1, img1, img2, h, w, nl, rgbs_detach_scale):
+    def forward(ctx, d1, d2, K, Rt, s1, img1, img2, h, w, nl, rgbs_detach_scale, with_ssim):
         ctx.set_materialize_grads(False)
         dev = d1.device
         P = h * w
@@ -29,8 +34,13 @@ class _PairTerms(torch.autograd.Function):
         work = torch.empty(nfl, device=dev, dtype=torch.float32)
         nn = torch.empty(2 * P, device=dev, dtype=torch.int32)
         out3 = torch.empty(3, device=dev, dtype=torch.float32)
-        _hip.pair_forward(d1c, d2c, h, w, Kc, Rtc, s1c, nl, i1, i2, work, nn, out3)
-        ctx.save_for_backward(d1c, d2c, Kc, Rtc, s1c, i1, i2, work, nn, out3)
+        samples = None
+        if with_ssim and i1 is not None:      # without images there is no rgb_s term to blend
+            samples = torch.empty(6 * P, device=dev, dtype=torch.float32)
+            _hip.pair_forward_ssim(d1c, d2c, h, w, Kc, Rtc, s1c, nl, i1, i2, work, nn, samples, out3)
+        else:
+            _hip.pair_forward(d1c, d2c, h, w, Kc, Rtc, s1c, nl, i1, i2, work, nn, out3)
+        ctx.save_for_backward(d1c, d2c, Kc, Rtc, s1c, i1, i2, work, nn, out3, samples)
         ctx.meta = (h, w, nl, int(rgbs_detach_scale), d1.shape, d2.shape, Rt.shape,
                     None if s1 is None else s1.shape)
         l_pc = out3[0].clone()
@@ -39,10 +49,10 @@ class _PairTerms(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_pc, g_rgbs):
-        d1c, d2c, Kc, Rtc, s1c, i1, i2, work, nn, out3 = ctx.saved_tensors
+        d1c, d2c, Kc, Rtc, s1c, i1, i2, work, nn, out3, samples = ctx.saved_tensors
         h, w, nl, det, sh1, sh2, shRt, shs = ctx.meta
         if g_pc is None and g_rgbs is None:
-            return (None,) * 11
+            return (None,) * 12
         dev = d1c.device
         P = h * w
         nb = (P + 255) // 256
@@ -53,9 +63,13 @@ class _PairTerms(torch.autograd.Function):
         want = ctx.needs_input_grad
         g_d1 = torch.empty(P, device=dev, dtype=torch.float32) if want[0] else None
         g_d2 = torch.empty(P, device=dev, dtype=torch.float32) if want[1] else None
-        _hip.pair_backward(d1c, d2c, h, w, Kc, Rtc, s1c, nl, i1 if g_rgbs is not None else None,
-                           i2 if g_rgbs is not None else None, det, work, nn, out3, c(g_pc), c(g_rgbs), gxy,
-                           g_d1, g_d2, g13, part)
+        if samples is not None and g_rgbs is not None:
+            _hip.pair_backward_ssim(d1c, d2c, h, w, Kc, Rtc, s1c, nl, i1, i2, det, work, nn, samples, out3, c(g_pc),
+                                    c(g_rgbs), gxy, g_d1, g_d2, g13, part)
+        else:
+            _hip.pair_backward(d1c, d2c, h, w, Kc, Rtc, s1c, nl, i1 if g_rgbs is not None else None,
+                               i2 if g_rgbs is not None else None, det, work, nn, out3, c(g_pc), c(g_rgbs), gxy,
+                               g_d1, g_d2, g13, part)
         gRt = None
         if want[3]:
             gRt = torch.zeros(4, 4, device=dev, dtype=torch.float32)
@@ -64,15 +78,16 @@ class _PairTerms(torch.autograd.Function):
             gRt = gRt.view(shRt)
         gs = g13[12:13].view(shs) if (want[4] and shs is not None) else None
         return (g_d1.view(sh1) if g_d1 is not None else None, g_d2.view(sh2) if g_d2 is not None else None,
-                None, gRt, gs, None, None, None, None, None, None)
+                None, gRt, gs, None, None, None, None, None, None, None)
 
 
-def pair_losses(d1, d2, camera_mat, Rt_rel, scale1, img1, img2, res, nl, rgbs_detach_scale=False):
+def pair_losses(d1, d2, camera_mat, Rt_rel, scale1, img1, img2, res, nl, rgbs_detach_scale=False, with_ssim=False):
     """(loss_pc, loss_rgb_s) of the image pair.  d1, d2: [1,1,h,w] depths at res (clamped);
-    img1, img2: [1,3,h,w] or None (no rgb_s term, returned as 0)."""
+    img1, img2: [1,3,h,w] or None (no rgb_s term, returned as 0).  with_ssim: training.with_ssim,
+    the SSIM-blended reprojection term."""
     h, w = res
     if camera_mat.requires_grad:
         raise ValueError("pair_losses: a learned camera matrix is not supported")
     return _PairTerms.apply(d1.reshape(-1), d2.reshape(-1), camera_mat.reshape(4, 4), Rt_rel.reshape(4, 4),
                             None if scale1 is None else scale1.reshape(1), img1, img2, int(h), int(w), float(nl),
-                            bool(rgbs_detach_scale))
+                            bool(rgbs_detach_scale), bool(with_ssim))
