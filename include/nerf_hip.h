@@ -131,7 +131,16 @@ int nerf_linear_bwd_data(const float* dy, int lddy, int k, const float* wt, cons
  * m % (32*splits) == 0.  dy_cmax [m/128][nout], x_cmax [m/128][kin] (optional, mode 2): upper
  * bounds of max |.| per column and 128-row group (as y_cmax of nerf_linear_fwd); given both and
  * splits of whole 128-row groups, mode 2 runs the fp16 pair kernel (column-scaled operands,
- * three products), else the bf16x3 one. */
+ * three products), else the bf16x3 one.
+ * The bounds set the scales and nothing else: a column's scale exponent is 141 - the biased
+ * exponent of its bound (the maximum of the split's groups), 140 for a subnormal bound, 0 for a
+ * bound of 0.  A loose bound is allowed and costs exactly its slack in absolute accuracy (a
+ * column at 1/8 of its bound keeps 3 bits fewer; nerf_encode_samples' bound 1 for every sin / cos
+ * column is such a bound).  A bound of 0 promises a column that is 0 throughout the group (the
+ * encodings' pad column, a ReLU-dead column); over non-zero data the result is unspecified (the
+ * column is split unscaled and may leave fp16's range).  A bound below the data is an error of
+ * the caller: the scaled column overflows fp16.  Where every product of an entry is 0 the entry
+ * is exactly 0 in every mode. */
 int nerf_linear_bwd_weight(const float* dy, int lddy, int nout, const float* x, int ldx,
                            int kin, int m, int splits, float* slab, int ldslab, int col0,
                            float* bslab, const float* dy_cmax, const float* x_cmax, void* stream);
@@ -305,7 +314,11 @@ int nerf_gemm_set_policy(int nt_policy, int tn_policy);
 /* f32 arithmetic of the GEMM family (process-wide; default 2 since ABI 9):
  *   0  exact-f32 v_mfma_f32_32x32x2_f32 (a k-ordered f32 fma chain);
  *   1  f32 emulated on v_mfma_f32_32x32x16_bf16: operands split into three bf16
- *      words (exact), the six cross products >= 2^-16 |a||b| accumulated in f32.
+ *      words (exact for |x| >= 2^-110: bf16 has f32's exponent range, so the low words of a
+ *      smaller operand round onto bf16's subnormal grid 2^-133 and an f32 subnormal keeps about
+ *      3 bits; nerf_linear_bwd_weight scales a column whose maximum over the split lies below
+ *      2^-33 or above 2^64 into [0.5, 1) itself, so there the limit is 2^-110 of the column
+ *      maximum), the six cross products >= 2^-16 |a||b| accumulated in f32.
  *      nerf_linear_fwd / nerf_linear_bwd_data use it when given the weight's split
  *      image (w_split / wt_split), nerf_linear_bwd_weight always.
  *   2  f32 emulated on v_mfma_f32_32x32x16_f16: every operand row (nerf_linear_fwd,
@@ -449,6 +462,9 @@ int nerf_heads_fwd(const float* h8, int ld8, const float* hr, int ldr, int hidde
                    float* raw4, int n_pad, void* stream);
 
 /* graw4[s] = dL/draw4[s].  Writes dyr = (graw4[s,1:4] @ Wc) * (hr > 0)  [n_pad][hidden/2]
+ * -- the gate is the f32 comparison: open for every positive value, subnormals included, closed
+ * (dyr exactly 0) for 0.0 and -0.0; the hr_mask bits of nerf_heads_bwd_mode are the same gate,
+ * as nerf_linear_fwd's mask_out writes them for the stored value --
  * and per-block partial sums of dWc (3 x hidden/2), dbc (3), dwd (hidden), dbd (1) into
  * part[blocks][4*hidden/2... ] -- see nerf_heads_part_size(). */
 int nerf_heads_part_size(int hidden, int n_pad);

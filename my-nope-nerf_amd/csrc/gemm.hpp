@@ -76,6 +76,8 @@ struct TNArgs {
     // fp16 pair kernel scales each split's columns by them
     const float* cm_dy; int ldcm_dy;
     const float* cm_x; int ldcm_x;
+    int cm_groups;   // rows of cm_dy / cm_x (m / 128) when both were given and m % 128 == 0, else 0: the
+                     // bf16x3 kernels take their column scales from them (gemm_x6.hip tn_col_exp3)
     unsigned long long* stamps;   // unused (the round-3 TN phase stamps were a diagnostic build)
 };
 

@@ -542,6 +542,65 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void k_gemm_nt_x6(NTArgs p) {
 // The strips of a k-tile can be loaded NS tiles ahead of the split that consumes them (NS
 // register sets; dispatch_tn_x6 picks the depth).
 
+// Column scales of the bf16x3 TN kernels.  bf16 shares f32's exponent range but has 8 significant
+// bits, so the mid / lo words of an operand below 2^-110 round onto bf16's subnormal grid 2^-133 and
+// a tiny column loses its low bits (an f32 subnormal keeps about 3).  A column whose maximum over the
+// split is below 2^-33 or above 2^64 is therefore scaled by the power of two that takes the maximum
+// into [0.5, 1) (exact; undone in the epilogue), so the three-word split is exact down to 2^-110 of
+// the column maximum.  A column in [2^-33, 2^64] (every operand of the field) is left as it is: the
+// same bits as without scales.  The maximum comes from the caller's per-group column bounds where
+// they were given (mode 2 falling back on splits that are no whole groups -- a training batch whose
+// rows per split are no multiple of 128 -- and mode 1 with bounds: a few loads per column, over the
+// groups the split touches); without bounds the block scans its operand panel once, every thread a
+// 16-byte piece of a row class, the partial maxima combined by LDS atomics (tn_scan_absmax).
+template <int COLS, int NT>
+__device__ __forceinline__ void tn_scan_absmax(const float* base, int ld, int rows, unsigned* lmax) {
+    constexpr int CG = COLS / 4;   // 16-byte column groups
+    static_assert(COLS % 4 == 0 && NT % CG == 0, "scan shape");
+    constexpr int G = NT / CG;     // row classes: thread (g, cg) takes rows g, g + G, ...
+    const int c4 = ((int)threadIdx.x % CG) * 4, g = (int)threadIdx.x / CG;
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto fold = [&](const float4& v) {
+        m.x = fmaxf(m.x, fabsf(v.x)); m.y = fmaxf(m.y, fabsf(v.y));
+        m.z = fmaxf(m.z, fabsf(v.z)); m.w = fmaxf(m.w, fabsf(v.w));
+    };
+    int r = g;
+    for (; r + 15 * G < rows; r += 16 * G) {   // sixteen 16-byte loads in flight
+        float4 v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = *reinterpret_cast<const float4*>(base + (size_t)(r + u * G) * ld + c4);
+#pragma unroll
+        for (int u = 0; u < 16; ++u) fold(v[u]);
+    }
+    for (; r < rows; r += G) fold(*reinterpret_cast<const float4*>(base + (size_t)r * ld + c4));
+    // |x| as an unsigned integer orders as |x| does (a NaN never enters: fmaxf drops it)
+    atomicMax(lmax + c4 + 0, __float_as_uint(m.x));
+    atomicMax(lmax + c4 + 1, __float_as_uint(m.y));
+    atomicMax(lmax + c4 + 2, __float_as_uint(m.z));
+    atomicMax(lmax + c4 + 3, __float_as_uint(m.w));
+}
+// the bound of column `col` over the groups that rows [s0, s0 + rows) touch (the split need not be whole groups)
+__device__ __forceinline__ float tn_colmax_cover(const float* cm, int ld, int groups, size_t s0, int rows, int col) {
+    int g = (int)(s0 / 128), g1 = (int)((s0 + rows + 127) / 128);
+    g1 = g1 < groups ? g1 : groups;
+    float m = 0.f;
+    for (; g + 8 <= g1; g += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = cm[(size_t)(g + u) * ld + col];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) m = fmaxf(m, v[u]);
+    }
+    for (; g < g1; ++g) m = fmaxf(m, cm[(size_t)g * ld + col]);
+    return m;
+}
+__device__ __forceinline__ int tn_col_exp3(float m) {
+    if (!(m > 0.f) || !(m <= 3.4028234664e38f)) return 0;
+    int ex;
+    (void)frexpf(m, &ex);   // m = f 2^ex, f in [0.5, 1)
+    return (ex >= -32 && ex <= 64) ? 0 : -ex;
+}
+
 template <int BM, int BN, int NT, bool HH = false, int NSET = 1>
 struct TNStager {
     static constexpr bool H = HH;       // fp16 pair images with per-column scales (mode 2)
@@ -558,10 +617,11 @@ struct TNStager {
     const float* dyb; const float* xb;
     int lddy, ldx;
     int offa[SA], offb[SB];
-    int ea[SA], eb[SB];                 // H: scale exponents of this thread's columns
+    int ea[SA], eb[SB];                 // scale exponents of this thread's columns (H: from the bounds; bf16x3: tn_col_exp3)
     float va[NS][SA][8], vb[NS][SB][8];
     float bsum[SA];
     bool do_bias;
+    bool scaled;                        // bf16x3: some column of the tile has a scale (block-uniform)
     __device__ __forceinline__ bool a_ok(int i) const { return SA * NT == 2 * BM || (int)threadIdx.x + NT * i < 2 * BM; }
     __device__ __forceinline__ bool b_ok(int i) const {
         return BQ || SB * NT == 2 * BN || (int)threadIdx.x + NT * i < 2 * BN;
@@ -571,7 +631,9 @@ struct TNStager {
     // (VGPR) and the row offset of each of its 8 loads in an SGPR, instead of 16 + 16
     // per-load 64-bit addresses
     __amdgpu_buffer_rsrc_t rdy, rx;
-    __device__ __forceinline__ void init(const TNArgs& p, size_t s0, int o0, int j0, bool bias) {
+    __device__ __forceinline__ void init(const TNArgs& p, size_t s0, int o0, int j0, bool bias, const int* lea,
+                                         const int* leb, bool any_scale) {
+        scaled = any_scale;
         lddy = p.lddy; ldx = p.ldx;
         dyb = p.dy + s0 * lddy + o0;
         xb = p.x + s0 * ldx + j0;
@@ -583,12 +645,14 @@ struct TNStager {
             offa[i] = 4 * (8 * (idx / BM) * lddy + idx % BM);
             bsum[i] = 0.f;
             if (H) ea[i] = row_exp(tn_colmax(p.cm_dy, p.ldcm_dy, s0, p.rows_per_split, o0 + idx % BM));
+            else ea[i] = a_ok(i) ? lea[idx % BM] : 0;   // bf16x3: the block's own column scales
         }
 #pragma unroll
         for (int i = 0; i < SB; ++i) {
             const int idx = threadIdx.x + NT * i;
             offb[i] = 4 * (RB * (idx / BN) * ldx + idx % BN);
             if (H) eb[i] = row_exp(tn_colmax(p.cm_x, p.ldcm_x, s0, p.rows_per_split, j0 + idx % BN));
+            else eb[i] = b_ok(i) ? leb[idx % BN] : 0;
         }
         do_bias = bias;
     }
@@ -619,7 +683,12 @@ struct TNStager {
             if (a_ok(i)) {
                 const int idx = threadIdx.x + NT * i;
                 if constexpr (H) put_col8h<BM>(Aimg, idx % BM, idx / BM, va[U][i], ea[i]);
-                else put_col8<BM>(Aimg, idx % BM, idx / BM, va[U][i]);
+                else if (scaled) {
+                    float sv[8];
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) sv[t] = __builtin_amdgcn_ldexpf(va[U][i][t], ea[i]);
+                    put_col8<BM>(Aimg, idx % BM, idx / BM, sv);
+                } else put_col8<BM>(Aimg, idx % BM, idx / BM, va[U][i]);
                 if (do_bias && count) {
                     float s = 0.f;
 #pragma unroll
@@ -633,7 +702,12 @@ struct TNStager {
                 const int idx = threadIdx.x + NT * i;
                 if constexpr (BQ) put_colRh<BN, RB>(Bimg, idx % BN, idx / BN, vb[U][i], eb[i]);
                 else if constexpr (H) put_col8h<BN>(Bimg, idx % BN, idx / BN, vb[U][i], eb[i]);
-                else put_col8<BN>(Bimg, idx % BN, idx / BN, vb[U][i]);
+                else if (scaled) {
+                    float sv[8];
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) sv[t] = __builtin_amdgcn_ldexpf(vb[U][i][t], eb[i]);
+                    put_col8<BN>(Bimg, idx % BN, idx / BN, sv);
+                } else put_col8<BN>(Bimg, idx % BN, idx / BN, vb[U][i]);
             }
     }
     template <int U>
@@ -752,7 +826,7 @@ __device__ __forceinline__ void tn_mainloop(char* smem, int nkt, int wm0, int wn
 // slab bytes of a 256 x 256 layer (twice the rows per split at the same block count)
 // without a second HBM read of dy.  Needs splits % 8 == 0.
 // LDS of one TN block: two operand image buffers (the epilogue's per-wave tiles reuse them),
-// + H: the tile's row / column scale exponents
+// + the tile's row / column scale exponents (both forms)
 template <int BM, int BN, int WM, int WN, bool H>
 struct TNSmem {
     static constexpr int NT = 64 * WM * WN;
@@ -762,7 +836,7 @@ struct TNSmem {
     static constexpr int LOOP = 2 * BUF;
     static constexpr int EPI = (NT / 64) * TileLds<TN>::BYTES;
     static constexpr int MAIN = LOOP > EPI ? LOOP : EPI;
-    static constexpr int BYTES = MAIN + (H ? (BM + BN) * 4 : 0);
+    static constexpr int BYTES = MAIN + (BM + BN) * 4;
 };
 
 // one TN block: output rows o0 .. o0 + BM, column tile jt (x columns jt BN ..), split `split`
@@ -783,22 +857,46 @@ __device__ __forceinline__ void tn_block(const TNArgs& p, char* smem, int o0, in
     const int nkt = p.rows_per_split / XK;
     const bool do_bias = (p.bslab != nullptr) && (jt == 0) && !(p.ablate & 4);
 
-    int* lea = reinterpret_cast<int*>(smem + MAIN_BYTES);   // H: scale exponents of the tile's rows / columns
+    int* lea = reinterpret_cast<int*>(smem + MAIN_BYTES);   // scale exponents of the tile's rows / columns
     int* leb = lea + BM;
     if (H) {   // published by the prologue's barrier
         for (int e = tid; e < BM; e += NT) lea[e] = row_exp(tn_colmax(p.cm_dy, p.ldcm_dy, s0, p.rows_per_split, o0 + e));
         for (int e = tid; e < BN; e += NT) leb[e] = row_exp(tn_colmax(p.cm_x, p.ldcm_x, s0, p.rows_per_split, j0 + e));
+    } else if (p.cm_groups > 0) {   // bf16x3 with the caller's bounds: the groups the split touches
+        for (int e = tid; e < BM; e += NT)
+            lea[e] = tn_col_exp3(tn_colmax_cover(p.cm_dy, p.ldcm_dy, p.cm_groups, s0, p.rows_per_split, o0 + e));
+        for (int e = tid; e < BN; e += NT)
+            leb[e] = tn_col_exp3(tn_colmax_cover(p.cm_x, p.ldcm_x, p.cm_groups, s0, p.rows_per_split, j0 + e));
+        __syncthreads();
+    } else {   // bf16x3 without bounds: one scan of the split's panel by the whole block
+        unsigned* lmax = reinterpret_cast<unsigned*>(lea);
+        for (int e = tid; e < BM + BN; e += NT) lmax[e] = 0u;
+        __syncthreads();
+        tn_scan_absmax<BM, NT>(p.dy + s0 * p.lddy + o0, p.lddy, p.rows_per_split, lmax);
+        tn_scan_absmax<BN, NT>(p.x + s0 * p.ldx + j0, p.ldx, p.rows_per_split, lmax + BM);
+        __syncthreads();
+        for (int e = tid; e < BM + BN; e += NT) lea[e] = tn_col_exp3(__uint_as_float(lmax[e]));
+        __syncthreads();
     }
+    // a tile none of whose columns has a scale -- every tile of the field's operands -- splits its strips
+    // without the eight ldexp per strip (block-uniform: one branch per strip, the split loop is VALU-bound)
+    bool any_scale = false;
+    if (!H) {
+        int nz = 0;
+        for (int e = tid; e < BM + BN; e += NT) nz |= lea[e];
+        any_scale = __syncthreads_or(nz) != 0;
+    }
+    // (nerf_gemm_debug_ablate bit 4, "skip the slab stores", takes tn_store: a thread sum of the scaled
+    // accumulators, scales not undone -- in the fp16 pair form and in this one alike)
     TnClock clk;
     clk.begin();
     TNStager<BM, BN, NT, H, NS> st;
-    st.init(p, s0, o0, j0, do_bias);
+    st.init(p, s0, o0, j0, do_bias, lea, leb, any_scale);
     f32x16 acc[TM][TN];
     zero_acc(acc);
     tn_mainloop<TM, TN, BM, BN>(smem, nkt, wm0, wn0, acc, st, clk);
 
-    if constexpr (H) tn_store_lds<TM, TN, true>(p, acc, smem, split, o0, j0, wm0, wn0, lea, leb);
-    else tn_store_lds(p, acc, smem, split, o0, j0, wm0, wn0);
+    tn_store_lds<TM, TN, true>(p, acc, smem, split, o0, j0, wm0, wn0, lea, leb);   // both forms undo their scales
     if (do_bias && !(p.ablate & 1)) {
         // strip (c, g) partial sums -> column sums, added in g order (deterministic)
         __syncthreads();

@@ -1502,3 +1502,299 @@ def pack_edge_rows(W):
     W[3] = W[3] / W[3].abs().max() * 1e-39
     W[4] = W[4] / W[4].abs().max() * 3e38
     return W
+
+
+# ---- the weight-gradient GEMMs and nerf_slab_reduce: fp64 references, derived ceilings, inputs ----------
+# From the text of include/nerf_hip.h (nerf_linear_bwd_weight, nerf_gemm_set_precision, nerf_slab_reduce):
+#   slab[split][o][col0 + j] = sum over the split's rows of dy[row, o] x[row, j],  bslab[split][o] = sum dy[row, o]
+# and, in precision mode 2, every column of a split scaled by the power of two of its bound (the maximum over
+# the split's 128-row groups of the passed column bounds), split into two fp16 words, three products.
+WGRAD_KINDS = ("generic", "spread", "zeros", "edge", "loose", "outlier", "exact")
+WGRAD_TIGHT = ("generic", "spread", "zeros", "loose")        # the kinds held to tight_bar
+F32_TINY = 2.0 ** -149                                       # the smallest f32 subnormal: an output's grid below 2^-126
+
+
+def wgrad_ref(dy, x, splits, _wrong=None):
+    """fp64 per-split slabs [splits][nout][kin], bias partials [splits][nout] and their condition sums
+    sum |dy||x| and sum |dy| over the split's rows -> (slab, bias, cond, bcond).
+    _wrong="row": the last row of every split left out."""
+    dy, x = _f64(dy), _f64(x)
+    m = dy.shape[0]
+    assert m % splits == 0 and x.shape[0] == m
+    D, X = dy.view(splits, m // splits, -1), x.view(splits, m // splits, -1)
+    if _wrong == "row":
+        D, X = D[:, :-1], X[:, :-1]
+    Dt = D.transpose(1, 2)
+    return Dt @ X, D.sum(1), Dt.abs() @ X.abs(), D.abs().sum(1)
+
+
+def wgrad_bounds(cmax, splits):
+    """Column bounds per 128-row group [m/128][cols] -> the bound of each split [splits][cols]: the maximum
+    over the split's groups (splits of whole groups)."""
+    g = cmax.shape[0]
+    assert g % splits == 0
+    return _f64(cmax).view(splits, g // splits, -1).amax(1)
+
+
+def wgrad_ceiling(rows, cond, dy_split, x_split, dy_bound=None, x_bound=None):
+    """pair_ceiling for one split's slab = dy^T x ([nout][kin], K = rows): the GEMM's operand rows are the
+    columns of dy and of x, and their maxima are replaced by the bounds the call was given (dy_bound [nout],
+    x_bound [kin]: the maximum over the split's groups of the passed column bounds), since the scales come
+    from the bounds -- a loose bound loosens the floor by exactly its slack:
+      (6 rows + 16) 2^-24 cond + 2^-37 (dy_bound[o] sum_s |x[s, j]| + sum_s |dy[s, o]| x_bound[j]) + 2^-149.
+    Without bounds (the exact-f32 and bf16x3 kernels: no scales, f32's own exponent range) the first term
+    alone.  2^-149 is the grid of an f32 output below 2^-126.  A condition, not a measurement."""
+    first = (6 * rows + 16) * U24 * cond + F32_TINY
+    if dy_bound is None:
+        return first
+    dy_split, x_split = _f64(dy_split).abs(), _f64(x_split).abs()
+    floor = _f64(dy_bound).unsqueeze(1) * x_split.sum(0).unsqueeze(0) + \
+        dy_split.sum(0).unsqueeze(1) * _f64(x_bound).unsqueeze(0)
+    return first + 2.0 ** -37 * floor
+
+
+def wgrad_bias_ceiling(rows, bcond):
+    """A bias partial is a plain f32 sum of the split's rows: dot_ceiling(rows, sum |dy|)."""
+    return dot_ceiling(rows, bcond) + F32_TINY
+
+
+def wgrad_reduced_ceiling(ceilings, slab_abs_sum, splits):
+    """A reduced gradient: the sum of its splits' ceilings plus the reduce's own (splits + 2) 2^-24 sum |slab|."""
+    return ceilings.sum(0) + (splits + 2) * U24 * slab_abs_sum
+
+
+def pair_exp(bound):
+    """The header's scale exponent of a bound (f32): 141 - biased exponent, 0 for a zero bound, 140 for a
+    subnormal one -- the bound times 2^e lies in [2^14, 2^15)."""
+    bits = bound.detach().cpu().float().contiguous().view(torch.int32).long()
+    ex = (bits >> 23) & 0xff
+    e = torch.where(ex > 0, 141 - ex, torch.full_like(ex, 140))
+    return torch.where(bound.detach().cpu().float() == 0, torch.zeros_like(e), e)
+
+
+def _pair_words(v, e):
+    """v (fp64 holding f32 values) scaled by 2^e -> (hi, lo) fp16 words as fp64: hi = fp16(v 2^e), lo =
+    fp16 of the remainder (exact in f32)."""
+    s = (v * torch.pow(torch.tensor(2.0, dtype=torch.float64), e.double())).float()
+    hi = s.half()
+    lo = (s - hi.float()).half()
+    return hi.double(), lo.double()
+
+
+def wgrad_pair_emulate(dy, x, dy_cmax, x_cmax, splits, _wrong=None):
+    """The fp16-pair arithmetic of precision mode 2 in fp64, per split: the columns' exponents from the
+    bounds (pair_exp of the maximum over the split's groups), the scaled operands as fp16 (hi, lo) words,
+    hi.lo + lo.hi + hi.hi formed exactly (fp64 holds every 22-bit product; the sum's own rounding is 2^-53),
+    the scales undone -> slabs [splits][nout][kin].  The representation error alone: no f32 accumulation.
+    _wrong="drop": the lo.hi product dropped; _wrong="split": the bounds of the next split."""
+    dy, x = _f64(dy), _f64(x)
+    m = dy.shape[0]
+    r = m // splits
+    bd, bx = wgrad_bounds(dy_cmax, splits).float(), wgrad_bounds(x_cmax, splits).float()
+    if _wrong == "split":
+        bd, bx = bd.roll(-1, 0), bx.roll(-1, 0)
+    out = []
+    for s in range(splits):
+        ea, eb = pair_exp(bd[s]), pair_exp(bx[s])
+        ah, al = _pair_words(dy[s * r:(s + 1) * r], ea.unsqueeze(0))
+        bh, bl = _pair_words(x[s * r:(s + 1) * r], eb.unsqueeze(0))
+        acc = ah.t() @ bl + ah.t() @ bh
+        if _wrong != "drop":
+            acc = acc + al.t() @ bh
+        out.append(acc * torch.pow(torch.tensor(2.0, dtype=torch.float64), -(ea.unsqueeze(1) + eb.unsqueeze(0)).double()))
+    return torch.stack(out)
+
+
+def _group_max(t, grp=128):
+    return t.abs().view(t.shape[0] // grp, grp, t.shape[1]).amax(1).contiguous()
+
+
+def _pm1(g, *shape):
+    return torch.rand(*shape, generator=g) * 2 - 1
+
+
+def _set_colmax(t, col, value, grp, exact=None):
+    """Column `col` scaled by `value` with one element of every group exactly +-exact (default: value), at a
+    row that is never the group's first."""
+    t[:, col] = t[:, col] * value
+    exact = value if exact is None else exact
+    for r0 in range(0, t.shape[0], grp):
+        t[r0 + (7 * col + 3) % grp, col] = exact if (r0 // grp) % 2 == 0 else -exact
+
+
+def wgrad_inputs(kind, m, nout, kin, seed, splits=1):
+    """(dy [m][nout], x [m][kin], dy_cmax [m/128][nout], x_cmax [m/128][kin]) as f32 CPU tensors; the bounds
+    are the exact group maxima unless the kind says otherwise, and None when m is no multiple of 128 (splits
+    shorter than a group run without scales).  `splits` places the split-wise zeros of kind "zeros".
+      generic  +-1 uniform; x clamped at 0 for an odd seed (a post-ReLU operand).
+      spread   column c of dy scaled by 2^k, k cycling through CRAFT_EXPS; x the same scales in another order
+               (column j: CRAFT_EXPS[(5 j + j // 6) % 6]), so every tile holds every pairing.
+      zeros    dy column 1 / x column 2 dead (zero everywhere, bound 0); dy column 3 / x column 5 zero in every
+               group of split 1 only; dy column 6 / x column 7 zero in the first 128-row group; dy entirely zero
+               in the last split (splits > 1); the last 5 rows zero in both (padding rows).
+      edge     dy: column 0 subnormal (maximum 2^-130), columns 1, 2, 3 with maxima exactly 2^-3, 1, 2^15,
+               column 4 zero but for +-3e38 (alternating) at the first row of every 128-row group.  x: column 0
+               subnormal, columns 1, 2, 3 with maxima exactly 2^-3, 1, 2^15, the upper half of the columns
+               <= 2^-100 (column kin / 2 with maximum exactly 2^-100), and every column <= 2^-100 in the rows
+               that carry a 3e38 (so no sum leaves f32's range).
+      loose    x: column j scaled by a true maximum in [0.3, 1] with bound 1 (the encoder's sin / cos convention),
+               the last column zero with bound 0 (its pad column); dy: bound = 8 x the true maximum.
+      outlier  dy[17][0] 2^20 above the rest of its column; x is 0 in the even columns of that row.
+      exact    dy[s][o] = 1 where o == s % nout, else 0; x[s][j] = (7 s + j) % 2048: every product and every
+               sum is an integer below 2^24, exact in every mode, and differs at every (split, o, j)."""
+    g = torch.Generator().manual_seed(seed)
+    grp = 128 if m % 128 == 0 else m // splits
+    r = m // splits
+    dy, x = _pm1(g, m, nout), _pm1(g, m, kin)
+    dcm = xcm = None
+    if kind == "generic":
+        if seed % 2:
+            x = x.clamp_min(0)
+    elif kind == "spread":
+        dy = dy * (2.0 ** torch.tensor([CRAFT_EXPS[c % 6] for c in range(nout)], dtype=torch.float32))
+        x = x * (2.0 ** torch.tensor([CRAFT_EXPS[(5 * j + j // 6) % 6] for j in range(kin)], dtype=torch.float32))
+    elif kind == "zeros":
+        dy[:, 1] = 0
+        x[:, 2] = 0
+        if splits > 1:
+            dy[r:2 * r, 3] = 0
+            x[r:2 * r, 5] = 0
+            dy[m - r:] = 0
+        dy[:grp, 6] = 0
+        x[:grp, 7] = 0
+        dy[m - 5:] = 0
+        x[m - 5:] = 0
+    elif kind == "edge":
+        big = torch.arange(0, m, grp)
+        for t in (dy, x):
+            _set_colmax(t, 0, 2.0 ** -130, grp)
+            _set_colmax(t, 1, 2.0 ** -3, grp)
+            _set_colmax(t, 3, 2.0 ** 15, grp)
+            _set_colmax(t, 2, 1.0, grp)
+        x[:, kin // 2:] *= 2.0 ** -100
+        _set_colmax(x, kin // 2, 1.0, grp, exact=2.0 ** -100)
+        x[big] = x[big].clamp(-2.0 ** -100, 2.0 ** -100)
+        dy[:, 4] = 0
+        dy[big, 4] = 3e38 * (1 - 2 * (torch.arange(len(big)) % 2)).float()
+    elif kind == "loose":
+        x = x * (0.3 + 0.7 * torch.rand(1, kin, generator=g))
+        x[:, kin - 1] = 0
+        if m % 128 == 0:
+            xcm = torch.ones(m // 128, kin)
+            xcm[:, kin - 1] = 0
+            dcm = 8 * _group_max(dy)
+    elif kind == "outlier":
+        dy[17, 0] = 2.0 ** 20
+        x[17, 0::2] = 0
+    elif kind == "exact":
+        s = torch.arange(m)
+        dy = (torch.arange(nout).unsqueeze(0) == (s % nout).unsqueeze(1)).float()
+        x = ((7 * s.unsqueeze(1) + torch.arange(kin).unsqueeze(0)) % 2048).float()
+    else:
+        raise ValueError(kind)
+    dy, x = dy.float().contiguous(), x.float().contiguous()
+    if m % 128 == 0:
+        dcm = _group_max(dy) if dcm is None else dcm
+        xcm = _group_max(x) if xcm is None else xcm
+        assert bool((dcm >= _group_max(dy)).all()) and bool((xcm >= _group_max(x)).all())      # bounds are bounds
+    return dy, x, dcm, xcm
+
+
+def slab_reduce_ref(slab, bslab, nout_ref, kin_ref, gw0=None, gb0=None):
+    """nerf_slab_reduce in fp64: slab [splits][nout][ldslab], bslab [splits][nout] (or None) -> (gw, gb,
+    cond_w, cond_b), gw [nout_ref][kin_ref] = sum over the splits (+ gw0 when accumulating), the condition
+    sums sum |slab| (+ |gw0|) per element."""
+    S = _f64(slab)[:, :nout_ref, :kin_ref]
+    gw, cw = S.sum(0), S.abs().sum(0)
+    if gw0 is not None:
+        gw, cw = gw + _f64(gw0), cw + _f64(gw0).abs()
+    gb = cb = None
+    if bslab is not None:
+        B = _f64(bslab)[:, :nout_ref]
+        gb, cb = B.sum(0), B.abs().sum(0)
+        if gb0 is not None:
+            gb, cb = gb + _f64(gb0), cb + _f64(gb0).abs()
+    return gw, gb, cw, cb
+
+
+def slab_reduce_bar(splits, cond):
+    """(splits + 2) 2^-24 sum |slab| per element: a sum of `splits` f32 terms in any order, the accumulated
+    gradient one more (+ the grid of an f32 output below 2^-126)."""
+    return (splits + 2) * U24 * cond + F32_TINY
+
+
+# ---- the head kernels (nerf_heads_fwd, nerf_heads_bwd_mode, nerf_heads_reduce) ------------------------------
+def heads_ref(h8, hr, wd, bd, wc, bc, graw4, dtype=torch.float64, _wrong=None):
+    """The header's formulas at a dtype:
+      raw4[s] = (h8[s].wd + bd, hr[s].wc[c] + bc[c]),  dyr = (graw4[s, 1:4] @ wc) * (hr > 0),
+      gwd = sum_s graw4[s, 0] h8[s], gbd = sum_s graw4[s, 0], gwc[c] = sum_s graw4[s, 1 + c] hr[s],
+      gbc[c] = sum_s graw4[s, 1 + c]
+    -> dict(raw4, dyr, rmax, cmax (n % 128 == 0, else None), gwd, gbd, gwc, gbc) and the condition sums
+    c_raw4, c_dyr, c_gwd, c_gbd, c_gwc, c_gbc (the same sums over absolute values).
+    _wrong="gate": the gate read as hr >= 0.  The result lives where hr lives (the 131 k cases: on the device)."""
+    c = lambda t: t.detach().to(hr.device, dtype)      # noqa: E731
+    h8, hr, wd, bd, wc, bc, G = c(h8), c(hr), c(wd).reshape(1, -1), c(bd).reshape(1), c(wc), c(bc), c(graw4)
+    n = hr.shape[0]
+    out = dict(raw4=torch.cat([h8 @ wd.t() + bd, hr @ wc.t() + bc], 1),
+               c_raw4=torch.cat([h8.abs() @ wd.abs().t() + bd.abs(), hr.abs() @ wc.abs().t() + bc.abs()], 1))
+    gate = hr >= 0 if _wrong == "gate" else hr > 0
+    out["gate"] = gate
+    out["dyr"] = (G[:, 1:] @ wc).masked_fill(~gate, 0.0)
+    out["c_dyr"] = (G[:, 1:].abs() @ wc.abs()).masked_fill(~gate, 0.0)
+    out["rmax"] = out["dyr"].abs().amax(1)
+    out["cmax"] = out["dyr"].abs().view(n // 128, 128, -1).amax(1) if n % 128 == 0 else None
+    out["gwd"], out["c_gwd"] = G[:, 0] @ h8, G[:, 0].abs() @ h8.abs()
+    out["gbd"], out["c_gbd"] = G[:, 0].sum().reshape(1), G[:, 0].abs().sum().reshape(1)
+    out["gwc"], out["c_gwc"] = G[:, 1:].t() @ hr, G[:, 1:].abs().t() @ hr.abs()
+    out["gbc"], out["c_gbc"] = G[:, 1:].sum(0), G[:, 1:].abs().sum(0)
+    return out
+
+
+def heads_sum_ceiling(n_pad, blocks, cond):
+    """The ceiling of a head-weight or head-bias sum, from the summation order of nerf_heads_bwd_mode 2 / 3
+    and nerf_heads_reduce: (chain + c) 2^-24 sum |term|.
+      chain = 128 ceil(chunks / (4 blocks)), chunks = ceil(n_pad / 128): a lane adds the rows of its wave's
+              128-row chunks to one accumulator, one rounding per row (an fma, or an add for the biases);
+      c = ceil(blocks / 8) + 8: the four waves of a block (3 adds), the reduce's walk over the blocks (each of
+          its four waves two chains of at most ceil(blocks / 8) partials, joined by 1 add), its four waves
+          (2 adds in a tree), the accumulated gradient (1, counted whether or not the call accumulates), and 1 for the
+          second-order terms.
+    `blocks` is nerf_heads_part_size / (hidden + 3 max(64, hidden / 2) + 4).  A condition, not a measurement."""
+    chunks = (n_pad + 127) // 128
+    chain = 128 * ((chunks + 4 * blocks - 1) // (4 * blocks))
+    c = (blocks + 7) // 8 + 8
+    return (chain + c) * U24 * cond + F32_TINY
+
+
+def heads_inputs(hidden, n_pad, seed, device="cpu"):
+    """Head operands with the edge rows and columns of the fp64 head tests, built on `device`:
+      hr  post-ReLU (+-1 clamped at 0), columns 3 and HR - 1 dead, and in rows 16 k + 1 .. 16 k + 3 the values
+          0.0, -0.0 and the smallest positive subnormal in column 5;
+      graw4  N(0, 1), each row scaled by 2^(+-30) or 1 (cycling), rows 16 k + 4 zero, 16 k + 5 sigma only,
+          16 k + 6 rgb only.
+    -> dict(h8, hr, wd, bd, wc, bc, graw4) f32, HR = max(64, hidden / 2)."""
+    HR = max(64, hidden // 2)
+    g = torch.Generator(device=device).manual_seed(seed)
+    rnd = lambda *s: torch.rand(*s, generator=g, device=device) * 2 - 1      # noqa: E731
+    h8 = torch.rand(n_pad, hidden, generator=g, device=device)
+    hr = rnd(n_pad, HR).clamp_min(0)
+    hr[:, 3] = 0
+    hr[:, HR - 1] = 0
+    hr[1::16, 5] = 0.0
+    hr[2::16, 5] = -0.0
+    hr[3::16, 5] = F32_TINY
+    graw4 = torch.randn(n_pad, 4, generator=g, device=device)
+    rows = torch.arange(n_pad, device=device)
+    graw4 = graw4 * (2.0 ** (30.0 * ((rows % 3) - 1).float())).unsqueeze(1)
+    graw4[4::16] = 0
+    graw4[5::16, 1:] = 0
+    graw4[6::16, 0] = 0
+    return dict(h8=h8, hr=hr, wd=rnd(1, hidden), bd=rnd(1), wc=rnd(3, HR), bc=rnd(3), graw4=graw4.contiguous())
+
+
+def relu_words(gate):
+    """bool [m][n] (n % 32 == 0) -> ReLU words [m][n / 32] int32, bit b of word w = column 32 w + b
+    (nerf_linear_fwd's mask_out layout)."""
+    m, n = gate.shape
+    w = (gate.long().view(m, n // 32, 32) << torch.arange(32, device=gate.device)).sum(-1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
