@@ -651,6 +651,57 @@ int nerf_camera_rays_bwd(const float* M, const float* pixels, const float* depth
                          const float* g_cam, const float* g_ray, const float* g_view, const float* g_norm,
                          const float* g_dsrc, float* gM, float* g_depth, void* stream);
 
+/* The head of a training step in ONE launch (additive entry, ABI version unchanged): the ray
+ * set-up before the per-sample work (training.py:277-288, rendering.py:52-98, common.py:13-40,
+ * :139-141, :205-208 and :277-310, poses.py:23-31, network.py:24-26) and the weight pack of
+ * nerf_pack_weights, which read nothing the other writes.  Block 0 (one workgroup) runs, in
+ * order and with the arithmetic of the entry named: c2w = nerf_pose_c2w(r, t, init_c2w) (or a
+ * copy of c2w_in when r is NULL); world = nerf_mat4_inv(c2w); M, inverses =
+ * nerf_unproject_matrix(K, world, scale); idx, pixels, rgb, status = nerf_sample_rays (same
+ * Philox counters, same seed_counter rule: read by all threads, advanced once); depth_g[j] =
+ * depth_map[idx[j]] (depth_map [n_pix] optional); depth_d = nerf_depth_affine(depth_g, aff_scale,
+ * aff_shift, shift_first, lo) (aff_scale optional); cam .. mask = nerf_camera_rays(M, pixels,
+ * depth_d or depth_g or NULL, flags).  Every result is bit for bit that of the separate entries.
+ * The other blocks run nerf_pack_weights' arithmetic over descs[0..n_desc).  rays == NULL: pack
+ * only; n_desc == 0: rays only.  The sampler's hash set is dynamic LDS sized from n_rays (a power
+ * of two >= 4 n_rays slots, 32 KB at 1024 rays); blocks never wait for one another.
+ * Required outputs: c2w, world, M, inverses, idx, pixels, rgb, cam, ray, ray_norm, d_src (and
+ * depth_g with depth_map, depth_d with aff_scale); status, view, mask are optional. */
+typedef struct {
+    const float* r;          /* [3] pose rotation (with t), or NULL: c2w_in is the pose */
+    const float* t;          /* [3] */
+    const float* init_c2w;   /* [4][4] or NULL (identity) */
+    const float* c2w_in;     /* [4][4], used when r == NULL */
+    const float* K;          /* [4][4] camera matrix */
+    const float* scale;      /* [4][4] scale matrix */
+    const float* img;        /* [3][height][width] */
+    const float* depth_map;  /* [n_pix] depth prior or NULL */
+    const float* aff_scale;  /* device scalar or NULL (no distortion) */
+    const float* aff_shift;  /* device scalar (with aff_scale) */
+    uint64_t* seed_counter;  /* optional, as nerf_sample_rays */
+    uint64_t seed;
+    int n_pix, n_rays, width, height;
+    int shift_first, flags;  /* flags: NERF_RAYS_* */
+    float lo;                /* nearest-limit clamp of the distorted depth (-INFINITY: none) */
+    float* c2w;              /* [4][4] */
+    float* world;            /* [4][4] */
+    float* M;                /* [4][4] */
+    float* inverses;         /* [3][4][4] */
+    int64_t* idx;            /* [n_rays] */
+    float* pixels;           /* [n_rays][2] */
+    float* rgb;              /* [n_rays][3] */
+    int* status;             /* optional */
+    float* depth_g;          /* [n_rays] gathered prior */
+    float* depth_d;          /* [n_rays] distorted prior */
+    float* cam;              /* [n_rays][3] */
+    float* ray;              /* [n_rays][3] */
+    float* view;             /* [n_rays][3], optional */
+    float* ray_norm;         /* [n_rays] */
+    float* d_src;            /* [n_rays] */
+    uint8_t* mask;           /* [n_rays], optional */
+} nerf_step_head_rays;
+int nerf_step_head(const nerf_step_head_rays* rays, const nerf_pack_desc* descs, int n_desc, void* stream);
+
 /* Loss.forward's render terms (losses.py:28-33, 60-66, 195-228), four device scalars:
  * total = w_rgb l_rgb + w_depth l_depth, l_rgb = sum|e| or sum e^2 over rgb [R][3] / R,
  * l_depth = sum over mask of |depth_pred - depth_gt| / max(count, 1), l2_mean = mean e^2;

@@ -44,11 +44,15 @@ __device__ inline void inverse4(const float in[16], float out[16]) {
 #pragma unroll
         for (int r = c + 1; r < 4; ++r)
             if (fabsf(a[r][c]) > best) { best = fabsf(a[r][c]); p = r; }
-        if (p != c) {
+        // the row swap with static indices only (a[p][j] with a run-time p puts the arrays in scratch
+        // once a kernel holds several inverses)
+#pragma unroll
+        for (int r = c + 1; r < 4; ++r) {
+            if (p != r) continue;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float t = a[c][j]; a[c][j] = a[p][j]; a[p][j] = t;
-                t = b[c][j]; b[c][j] = b[p][j]; b[p][j] = t;
+                float t = a[c][j]; a[c][j] = a[r][j]; a[r][j] = t;
+                t = b[c][j]; b[c][j] = b[r][j]; b[r][j] = t;
             }
         }
         const float piv = a[c][c];

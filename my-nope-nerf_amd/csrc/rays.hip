@@ -14,45 +14,14 @@
 // All are launch-latency bound (a few KB per step); the point is the launch count.
 #include "common.hpp"
 #include "mat4.hpp"
+#include "rays_dev.hpp"
 
 #include <cmath>
 
 namespace nerf {
 
-// ------------------------------------------------------------------------------------
-// Philox-4x32-10 (Salmon et al., SC'11), the counter-based generator torch's CUDA/HIP RNG
-// also uses; keyed by the host seed, counter = (ray slot, round, stream, 0).
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint32_t hi0 = __umulhi(M0, c.x), lo0 = M0 * c.x;
-        const uint32_t hi1 = __umulhi(M1, c.z), lo1 = M1 * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-        k.x += W0;
-        k.y += W1;
-    }
-    return c;
-}
-
-// uniform integer in [0, n) from 64 random bits: floor(u * n / 2^64) (bias < n / 2^64)
-__device__ __forceinline__ uint32_t uniform_below(uint4 r, uint32_t n) {
-    const uint64_t u = ((uint64_t)r.x << 32) | r.y;
-    return (uint32_t)__umul64hi(u, (uint64_t)n);
-}
-
-constexpr int SR_THREADS = 1024;
-constexpr int SR_LOG_TABLE = 14;
-constexpr int SR_TABLE = 1 << SR_LOG_TABLE;     // hash slots; load factor <= 1/4 at SR_MAX
-constexpr int SR_PER_THREAD = NERF_SAMPLE_MAX_RAYS / SR_THREADS;
-constexpr uint32_t SR_EMPTY = 0xFFFFFFFFu;
-constexpr int SR_MAX_ROUNDS = NERF_SAMPLE_MAX_ROUNDS;
-
-// R distinct pixel indices drawn uniformly from [0, n_pix) -- the set randperm(n)[:R]
-// returns, with its own (deterministic) generator.  Each pending ray slot draws a
-// candidate, inserts it into an LDS hash set (linear probing), and the slot whose
-// (round, slot) key is smallest owns the value; the others draw again next round.  The
-// outcome depends only on (seed, n, R), never on wave timing.
+// One workgroup: the draw (rays_dev.hpp sample_draw, the hash set in 2 x 64 KB of LDS), then the
+// pixel / colour gathers.
 __global__ __launch_bounds__(SR_THREADS) void k_sample_rays(int n_pix, int R, uint2 key, int width, int height,
                                                             const float* __restrict__ img,
                                                             int64_t* __restrict__ idx, float* __restrict__ pix,
@@ -64,68 +33,17 @@ __global__ __launch_bounds__(SR_THREADS) void k_sample_rays(int n_pix, int R, ui
     // device step counter (graph replays): the key mixes in the counter, thread 0 advances it
     // once every thread has read it (the kernel is a single workgroup)
     const unsigned long long c = ctr ? *ctr : 0ull;
-    if (ctr) {
-        const unsigned long long m = (c + 1) * 0x9E3779B97F4A7C15ull;
-        key.x ^= (uint32_t)m;
-        key.y ^= (uint32_t)(m >> 32);
-    }
-    for (int i = tid; i < SR_TABLE; i += SR_THREADS) {
-        table[i] = SR_EMPTY;
-        owner[i] = 0xFFFFFFFFu;
-    }
-    __syncthreads();
-    uint32_t val[SR_PER_THREAD], pos[SR_PER_THREAD];
+    if (ctr) key = sample_key_mix(key, c);
+    uint32_t val[SR_PER_THREAD];
     bool pend[SR_PER_THREAD];
-#pragma unroll
-    for (int q = 0; q < SR_PER_THREAD; ++q) pend[q] = (tid + q * SR_THREADS) < R;
-    int round = 0, done = 0;
-    for (; round < SR_MAX_ROUNDS; ++round) {
-#pragma unroll
-        for (int q = 0; q < SR_PER_THREAD; ++q) {
-            if (!pend[q]) continue;
-            const uint32_t slot = tid + q * SR_THREADS;
-            const uint32_t v = uniform_below(philox4x32_10(make_uint4(slot, round, 0x5a4d, 0), key), n_pix);
-            val[q] = v;
-            uint32_t h = (v * 2654435761u) >> (32 - SR_LOG_TABLE);
-            while (true) {
-                const uint32_t old = atomicCAS(&table[h], SR_EMPTY, v);
-                if (old == SR_EMPTY || old == v) break;
-                h = (h + 1) & (SR_TABLE - 1);
-            }
-            pos[q] = h;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < SR_PER_THREAD; ++q)
-            if (pend[q]) atomicMin(&owner[pos[q]], (uint32_t)(round * NERF_SAMPLE_MAX_RAYS + tid + q * SR_THREADS));
-        __syncthreads();
-        int any = 0;
-#pragma unroll
-        for (int q = 0; q < SR_PER_THREAD; ++q) {
-            if (!pend[q]) continue;
-            if (owner[pos[q]] == (uint32_t)(round * NERF_SAMPLE_MAX_RAYS + tid + q * SR_THREADS)) pend[q] = false;
-            else any = 1;
-        }
-        if (!__syncthreads_or(any)) { done = 1; break; }
-    }
-    if (tid == 0 && status != nullptr) *status = done ? round + 1 : 0;   // rounds used, 0 = gave up
-    const int hw = width * height;
+    const int st = sample_draw<SR_THREADS>(n_pix, R, key, table, owner, SR_LOG_TABLE, val, pend);
+    if (tid == 0 && status != nullptr) *status = st;   // rounds used, 0 = gave up
 #pragma unroll
     for (int q = 0; q < SR_PER_THREAD; ++q) {
         const int j = tid + q * SR_THREADS;
         if (j >= R) continue;
-        const uint32_t v = pend[q] ? 0u : val[q];
-        idx[j] = v;
-        if (pix != nullptr) {   // arange_pixels: 2*col/(W-1) - 1, 2*row/(H-1) - 1 (common.py:36-39)
-            const int row = v / width, col = v - row * width;
-            pix[2 * j] = 2.f * (float)col / (float)(width - 1) - 1.f;
-            pix[2 * j + 1] = 2.f * (float)row / (float)(height - 1) - 1.f;
-        }
-        if (rgb != nullptr) {   // img.view(1,3,H*W).permute(0,2,1)[:, idx]
-            rgb[3 * j] = img[v];
-            rgb[3 * j + 1] = img[hw + v];
-            rgb[3 * j + 2] = img[2 * hw + v];
-        }
+        float px, py;
+        sample_gather(j, pend[q] ? 0u : val[q], width, height, img, idx, pix, rgb, px, py);
     }
     if (ctr != nullptr) {
         __syncthreads();
@@ -142,37 +60,13 @@ __global__ void k_mat4_inv(const float* __restrict__ a, int n, float* __restrict
     store4(out + 16 * (size_t)i, r);
 }
 
-// c2w = [Exp(r) | t; 0 0 0 1] @ init (common.py:290-310, poses.py:27-30);
-// Exp(r) = I + sin(th)/th [r]x + (1 - cos th)/th^2 [r]x^2,  th = |r| + 1e-15
+// c2w = [Exp(r) | t; 0 0 0 1] @ init (rays_dev.hpp pose_c2w_eval), one thread
 __global__ void k_pose_c2w(const float* __restrict__ r, const float* __restrict__ t,
                            const float* __restrict__ init, float* __restrict__ out) {
-#pragma clang fp contract(off)
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const float x = r[0], y = r[1], z = r[2];
-    const float th = sqrtf(x * x + y * y + z * z) + 1e-15f;
-    const float K[9] = {0.f, -z, y, z, 0.f, -x, -y, x, 0.f};
-    float KK[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) KK[3 * i + j] = K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j] + K[3 * i + 2] * K[6 + j];
-    const float s = sinf(th) / th, c = (1.f - cosf(th)) / (th * th);
-    float m[16];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) m[4 * i + j] = ((i == j ? 1.f : 0.f) + s * K[3 * i + j]) + c * KK[3 * i + j];
-        m[4 * i + 3] = t[i];
-    }
-    m[12] = 0.f; m[13] = 0.f; m[14] = 0.f; m[15] = 1.f;
-    if (init != nullptr) {
-        float b[16], o[16];
-        load4(init, b);
-        matmul4(m, b, o);
-        store4(out, o);
-    } else {
-        store4(out, m);
-    }
+    float o[16];
+    pose_c2w_eval(r, t, init, o);
+    store4(out, o);
 }
 
 // Backward of k_pose_c2w (the closed form of torch autograd through common.py:277-310):
@@ -341,12 +235,9 @@ constexpr int AF_THREADS = 1024;
 __global__ __launch_bounds__(AF_THREADS) void k_depth_affine(const float* __restrict__ d, int n,
                                                              const float* __restrict__ s, const float* __restrict__ t,
                                                              int shift_first, float lo, float* __restrict__ y) {
-#pragma clang fp contract(off)
     const float sc = s[0], sh = t[0];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float v = shift_first ? (d[i] + sh) * sc : d[i] * sc + sh;
-        y[i] = v < lo ? lo : v;
-    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        y[i] = depth_affine_eval(d[i], sc, sh, shift_first, lo);
 }
 __global__ __launch_bounds__(AF_THREADS) void k_depth_affine_bwd(const float* __restrict__ d, int n,
                                                                  const float* __restrict__ s,
@@ -381,15 +272,11 @@ __global__ __launch_bounds__(AF_THREADS) void k_depth_affine_bwd(const float* __
 __global__ void k_unproject(const float* __restrict__ K, const float* __restrict__ world,
                             const float* __restrict__ scale, float* __restrict__ M, float* __restrict__ inverses) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    float a[16], ki[16], wi[16], si[16], t[16], m[16];
-    load4(K, a);
-    inverse4(a, ki);
-    load4(world, a);
-    inverse4(a, wi);
-    load4(scale, a);
-    inverse4(a, si);
-    matmul4(si, wi, t);
-    matmul4(t, ki, m);
+    float k[16], w[16], sc[16], ki[16], wi[16], si[16], m[16];
+    load4(K, k);
+    load4(world, w);
+    load4(scale, sc);
+    unproject_eval(k, w, sc, m, ki, wi, si);
     store4(M, m);
     if (inverses != nullptr) {
         store4(inverses, ki);
@@ -410,43 +297,12 @@ __global__ __launch_bounds__(CR_THREADS) void k_camera_rays(const float* __restr
                                                             float* __restrict__ cam, float* __restrict__ ray,
                                                             float* __restrict__ view, float* __restrict__ ray_norm,
                                                             float* __restrict__ d_src, uint8_t* __restrict__ mask) {
-#pragma clang fp contract(off)
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
     float M[16];
     load4(Mg, M);
-    const float x = pix[2 * r], y = pix[2 * r + 1];
-    float v[3], n2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        v[i] = (M[4 * i] * x + M[4 * i + 1] * y) + M[4 * i + 2];
-        n2 = n2 + v[i] * v[i];
-    }
-    const float n = sqrtf(n2);
-    const bool normalise = flags & NERF_RAYS_NORMALISE;
-    float ds = 1.f;   // no depth prior: d_src = 1 under either flag (the backward takes it as constant)
-    if (depth != nullptr) {
-        const float d = depth[r];
-        const float xd = x * d, yd = y * d;
-        float q2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float pi = (M[4 * i] * xd + M[4 * i + 1] * yd) + M[4 * i + 2] * d;
-            q2 = q2 + pi * pi;
-        }
-        ds = sqrtf(q2);
-        if (!normalise) ds = ds / n;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float di = normalise ? v[i] / n : v[i];
-        cam[3 * r + i] = M[4 * i + 3];
-        ray[3 * r + i] = di;
-        if (view != nullptr) view[3 * r + i] = (flags & NERF_RAYS_VIEW_ONES) ? 1.f : -di;
-    }
-    ray_norm[r] = n;
-    d_src[r] = ds;
-    if (mask != nullptr) mask[r] = (isfinite(ds) && ds != 0.f) ? 1 : 0;
+    camera_ray_eval(M, pix[2 * r], pix[2 * r + 1], depth != nullptr, depth != nullptr ? depth[r] : 0.f, r, flags,
+                    cam, ray, view, ray_norm, d_src, mask);
 }
 
 // Backward: gradient of (cam, ray, view, ray_norm, d_src) w.r.t. M (16, rows 3 stay 0) and

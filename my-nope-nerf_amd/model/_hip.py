@@ -39,6 +39,17 @@ class PackDesc(ctypes.Structure):
                 ("rows_s", _c_i), ("dst_cs", _c_p), ("dst_cts", _c_p), ("perm_k", _c_i)]
 
 
+class StepHeadRays(ctypes.Structure):
+    """nerf_step_head_rays (include/nerf_hip.h): the ray block's arguments."""
+    _fields_ = [("r", _c_p), ("t", _c_p), ("init_c2w", _c_p), ("c2w_in", _c_p), ("K", _c_p), ("scale", _c_p),
+                ("img", _c_p), ("depth_map", _c_p), ("aff_scale", _c_p), ("aff_shift", _c_p), ("seed_counter", _c_p),
+                ("seed", ctypes.c_uint64), ("n_pix", _c_i), ("n_rays", _c_i), ("width", _c_i), ("height", _c_i),
+                ("shift_first", _c_i), ("flags", _c_i), ("lo", _c_f), ("c2w", _c_p), ("world", _c_p), ("M", _c_p),
+                ("inverses", _c_p), ("idx", _c_p), ("pixels", _c_p), ("rgb", _c_p), ("status", _c_p),
+                ("depth_g", _c_p), ("depth_d", _c_p), ("cam", _c_p), ("ray", _c_p), ("view", _c_p),
+                ("ray_norm", _c_p), ("d_src", _c_p), ("mask", _c_p)]
+
+
 class ProfKind(ctypes.Structure):
     """nerf_prof_kind (include/nerf_hip.h)."""
     _fields_ = [("ms", ctypes.c_double), ("launches", _c_i64), ("flops", ctypes.c_double),
@@ -164,6 +175,7 @@ _SIGS = {
     "nerf_depth_affine_bwd": ([_c_p, _c_i, _c_p, _c_p, _c_i, _c_f, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_camera_rays": ([_c_p, _c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_camera_rays_bwd": ([_c_p, _c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_step_head": ([ctypes.POINTER(StepHeadRays), ctypes.POINTER(PackDesc), _c_i, _c_p], _c_i),
     "nerf_ray_loss": ([_c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_i, _c_i, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p,
                        _c_p], _c_i),
     "nerf_ray_loss_bwd": ([_c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_i, _c_i, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p,
@@ -558,6 +570,20 @@ def camera_rays(M, pixels, depth, n_rays, flags, cam, ray, view, ray_norm, d_src
 def camera_rays_bwd(M, pixels, depth, n_rays, flags, g_cam, g_ray, g_view, g_norm, g_dsrc, gM, g_depth):
     _call("nerf_camera_rays_bwd", _ptr(M), _ptr(pixels), _ptr(depth), int(n_rays), int(flags), _ptr(g_cam),
           _ptr(g_ray), _ptr(g_view), _ptr(g_norm), _ptr(g_dsrc), _ptr(gM), _ptr(g_depth), _stream())
+
+
+def step_head(rays: Optional[StepHeadRays], descs: Sequence[PackDesc] = ()):
+    """The head of a training step in one launch: the ray set-up (rays: device pointers as
+    integers, see step_head_rays) beside the weight pack of pack_weights (descs).  Either part
+    may be absent."""
+    arr = (PackDesc * len(descs))(*descs) if len(descs) else None
+    _call("nerf_step_head", None if rays is None else ctypes.byref(rays), arr, len(descs), _stream())
+
+
+def step_head_rays(**kw) -> StepHeadRays:
+    """StepHeadRays from keyword arguments: tensors become checked device pointers."""
+    return StepHeadRays(**{k: (_ptr(v) if isinstance(v, torch.Tensor) else v) for k, v in kw.items()
+                           if v is not None})
 
 
 def ray_loss(rgb, rgb_gt, n_rays, depth_pred, depth_gt, mask, n_depth, rgb_l1, w_rgb, w_depth, out, cnt):

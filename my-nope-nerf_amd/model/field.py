@@ -93,6 +93,10 @@ class FieldRunner:
         # the all-reduce and at the start of every step (release_grad_buffer)
         self.grad_buffer = None
         self.grad_buffer_taken = False
+        # one-shot mark "packed by the step head" (Trainer.compute_loss): the next forward consumes
+        # it and skips pack().  A flag, not a tensor version: HipAdam updates the flat parameter
+        # buffer through ctypes, which bumps no version counter
+        self.prepacked = False
 
     # ------------------------------------------------------------------ packing
     def _alloc(self, device):
@@ -116,6 +120,18 @@ class FieldRunner:
         self.device = device
 
     def pack(self):
+        _hip.pack_weights(self.pack_descs())
+
+    def ensure_packed(self):
+        """pack(), unless the step head packed these weights in its launch (the mark is consumed)."""
+        if self.prepacked:
+            self.prepacked = False
+            return
+        self.pack()
+
+    def pack_descs(self):
+        """The descriptor list of pack() (nerf_pack_weights / nerf_step_head); allocates the
+        destinations on first use and notes the GEMM precision mode they are packed for."""
         dev = self.m.layers0[0].weight.device
         if dev.type != "cuda":
             raise RuntimeError("nerf_hip: the field must live on the GPU (no CPU fallback)")
@@ -145,7 +161,7 @@ class FieldRunner:
         descs.append(_hip.PackDesc(wc.data_ptr(), self.wc.data_ptr(), None, 3, wc.shape[1], self.HR, 0, 0))
         wd = self.m.fc_density.weight
         descs.append(_hip.PackDesc(wd.data_ptr(), self.wd.data_ptr(), None, 1, wd.shape[1], self.D, 0, 0))
-        _hip.pack_weights(descs)
+        return descs
 
     def bias(self, l: LayerSpec):
         return self.bias_p[l.name]
@@ -162,7 +178,7 @@ class FieldRunner:
         dev = pts_o.device
         D, HR = self.D, self.HR
         e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-        self.pack()
+        self.ensure_packed()
         z = e(Np)
         enc_p = e(Np, _hip.ENC_P)
         enc_d = e(Np, _hip.ENC_D)
@@ -276,7 +292,7 @@ class FieldRunner:
         Np = _pad_rows(N)
         dev = pts_o.device
         e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-        self.pack()
+        self.ensure_packed()
         z, enc_p, enc_d = e(Np), e(Np, _hip.ENC_P), e(Np, _hip.ENC_D)
         enc_p_rm, enc_d_rm = e(Np), e(Np)
         _hip.encode_samples(pts_o, pts_d, view, noise, R, S, Np, near, far, z, enc_p, enc_d,
@@ -346,7 +362,7 @@ class FieldRunner:
         """-> rgb [R,3], dist [R], alpha [R,S], z [R,S] in one launch (no saved state)."""
         R = pts_o.shape[0]
         dev = pts_o.device
-        self.pack()
+        self.ensure_packed()
         descs = [_hip.ChainLayer(self.wsc[l.name].data_ptr(), self.wsc[l.name].shape[2], self.bias(l).data_ptr(),
                                  None, l.out_p, None, l.out_p // 32, None) for l in self.layers]
         e = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)

@@ -14,12 +14,16 @@ class nope_nerf(nn.Module):
         self.device = device
 
     def forward(self, p, ray_idx, camera_mat, world_mat, scale_mat, rendering_technique, it=0, eval_mode=False,
-                depth_img=None, add_noise=True, img_size=None, depth_affine=None, **kw):
+                depth_img=None, add_noise=True, img_size=None, depth_affine=None, rays=None, **kw):
         """network.py:19-33: area-resize the depth prior to the image size, gather it at
         the sampled rays, render.  depth_affine (MI355X build): a function applied to the
-        gathered values (the Trainer's scale / shift, commuted past the gather)."""
+        gathered values (the Trainer's scale / shift, commuted past the gather).  rays (MI355X
+        build): the camera rays of these pixels, already built with the prior gathered and
+        distorted (the Trainer's step head); the renderer takes them as they are."""
         depth = None
-        if rendering_technique == "nope_nerf":
+        if rays is not None:
+            kw["rays"] = rays
+        elif rendering_technique == "nope_nerf":
             d = depth_img
             if tuple(d.shape[-2:]) != tuple(img_size):
                 d = F.interpolate(d, img_size, mode="area")     # identity when already H x W

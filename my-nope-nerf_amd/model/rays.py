@@ -14,6 +14,8 @@ preparation, CPU tools) use the torch expressions of the reference functions.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import _hip
@@ -248,6 +250,115 @@ def camera_rays_hip(M, pixels, depth, normalise_ray=True, view_ones=False):
     """(cam, ray, view, ray_norm, d_src, mask) of pixels [1,R,2], depth [1,R,1] or None."""
     flags = (_hip.RAYS_NORMALISE if normalise_ray else 0) | (_hip.RAYS_VIEW_ONES if view_ones else 0)
     return _CameraRays.apply(M, pixels, depth, flags)
+
+
+# ------------------------------------------------------------------ the step head
+def step_head_enabled() -> bool:
+    """NERF_STEP_HEAD (default 1; 0 = the separate launches), read at call time."""
+    return os.environ.get("NERF_STEP_HEAD", "1") != "0"
+
+
+class _StepHead(torch.autograd.Function):
+    """pose_c2w, inv, sample_rays, the depth-prior gather (+ depth_affine), unproject_matrix and
+    camera_rays -- and the field's weight pack beside them -- as one launch (nerf_step_head).
+    The backward is the separate backward launches in the order autograd runs them today."""
+
+    @staticmethod
+    def forward(ctx, r, t, init, c2w_in, K, scale_mat, aff_scale, aff_shift, a):
+        ctx.set_materialize_grads(False)
+        img, depth_map, R = a["img"], a["depth_map"], a["n_rays"]
+        dev = img.device
+        e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+        c2w, world, M, invs = e(4, 4), e(1, 4, 4), e(4, 4), e(3, 4, 4)
+        idx = torch.empty(R, device=dev, dtype=torch.int64)
+        pix, rgb = e(1, R, 2), e(1, R, 3)
+        cam, ray, view, ray_norm, d_src = e(R, 3), e(R, 3), e(R, 3), e(R), e(R)
+        mask = torch.empty(R, device=dev, dtype=torch.bool)
+        depth_g = e(R) if depth_map is not None else None
+        affine = depth_map is not None and aff_scale is not None
+        depth_d = e(R) if affine else None
+        c = lambda x: None if x is None else _f32c(x)
+        rc, tc, ic, sc, tc2 = c(r), c(t), c(init), c(aff_scale) if affine else None, c(aff_shift) if affine else None
+        args = _hip.step_head_rays(
+            r=rc, t=tc, init_c2w=ic, c2w_in=c(c2w_in) if r is None else None, K=_f32c(K), scale=_f32c(scale_mat),
+            img=_f32c(img), depth_map=c(depth_map), aff_scale=sc, aff_shift=tc2, seed_counter=a["seed_counter"],
+            seed=int(a["seed"]) & 0xFFFFFFFFFFFFFFFF, n_pix=a["n_pix"], n_rays=R, width=a["width"],
+            height=a["height"], shift_first=int(bool(a["shift_first"])), flags=a["flags"], lo=float("-inf"),
+            c2w=c2w, world=world, M=M, inverses=invs, idx=idx, pixels=pix, rgb=rgb, depth_g=depth_g,
+            depth_d=depth_d, cam=cam, ray=ray, view=view, ray_norm=ray_norm, d_src=d_src, mask=mask)
+        _hip.step_head(args, a["descs"])
+        depth = depth_d if affine else depth_g
+        ctx.save_for_backward(rc, ic, world, M, invs, pix, depth, depth_g, sc, tc2)
+        ctx.meta = (R, a["flags"], int(bool(a["shift_first"])), affine, K.shape, scale_mat.shape,
+                    None if aff_scale is None else aff_scale.shape, None if aff_shift is None else aff_shift.shape,
+                    None if r is None else (r.shape, t.shape))
+        ctx.mark_non_differentiable(idx, pix, rgb, mask)
+        return c2w, world, idx, pix, rgb, cam, ray, view, ray_norm, d_src, mask
+
+    @staticmethod
+    def backward(ctx, g_c2w, g_world, g_idx, g_pix, g_rgb, g_cam, g_ray, g_view, g_norm, g_dsrc, g_mask):
+        rc, ic, world, M, invs, pix, depth, depth_g, sc, tc2 = ctx.saved_tensors
+        R, flags, shift_first, affine, Ksh, Ssh, assh, atsh, rtsh = ctx.meta
+        need = ctx.needs_input_grad     # r, t, init, c2w_in, K, scale_mat, aff_scale, aff_shift, a
+        if need[2]:
+            raise RuntimeError("step head: a learned init_c2w takes the separate launches")
+        dev = pix.device
+        c = lambda g: None if g is None else g.float().contiguous()
+        e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+        want_pose = need[0] or need[1] or need[3]
+        want_M = want_pose or need[4] or need[5]
+        want_aff = affine and (need[6] or need[7])
+        from_rays = any(g is not None for g in (g_cam, g_ray, g_view, g_norm, g_dsrc))
+        gM = g_depth = None
+        if from_rays and (want_M or want_aff):          # _CameraRays.backward
+            gM = e(4, 4)
+            g_depth = e(R) if want_aff else None
+            _hip.camera_rays_bwd(M, pix, depth, R, flags, c(g_cam), c(g_ray), c(g_view), c(g_norm), c(g_dsrc), gM,
+                                 g_depth)
+        gs = gt = None
+        if g_depth is not None:                         # _DepthAffine.backward
+            gs = e(1) if need[6] else None
+            gt = e(1) if need[7] else None
+            _hip.depth_affine_bwd(depth_g, sc, tc2, shift_first, float("-inf"), g_depth, gs, gt)
+        gK = gW = gS = None
+        if gM is not None and want_M:                   # _Unproject.backward
+            gK, gW, gS = (e(4, 4) if need[4] else None), (e(4, 4) if want_pose else None), (e(4, 4) if need[5] else None)
+            _hip.unproject_matrix_bwd(invs, gM, gK, gW, gS)
+        g_r = g_t = g_in = None
+        if want_pose:
+            gw = gW.view(1, 4, 4) if gW is not None else None
+            if g_world is not None:                     # the world matrix's other consumers (pair terms)
+                gw = c(g_world) if gw is None else gw + g_world
+            g_pose = None
+            if gw is not None:                          # _Inv4.backward
+                g_pose = e(1, 4, 4)
+                _hip.mat4_inv_bwd(world, _f32c(gw), g_pose)
+                g_pose = g_pose.view(4, 4)
+            if g_c2w is not None:
+                g_pose = c(g_c2w) if g_pose is None else g_pose + g_c2w
+            if g_pose is not None:
+                if rtsh is None:
+                    g_in = g_pose
+                else:                                   # _PoseC2W.backward
+                    g_r = e(3) if need[0] else None
+                    g_t = e(3) if need[1] else None
+                    _hip.pose_c2w_bwd(rc, ic, _f32c(g_pose), g_r, g_t)
+                    g_r = g_r.view(rtsh[0]) if g_r is not None else None
+                    g_t = g_t.view(rtsh[1]) if g_t is not None else None
+        return (g_r, g_t, None, g_in, gK.reshape(Ksh) if gK is not None else None,
+                gS.reshape(Ssh) if gS is not None else None, gs.view(assh) if gs is not None else None,
+                gt.view(atsh) if gt is not None else None, None)
+
+
+def step_head(pose, c2w_in, K, scale_mat, aff, a):
+    """One launch for the head of a training step.  pose = (r, t, init_c2w) or None with c2w_in
+    [4,4]; aff = (scale, shift) or None; a: the non-tensor arguments and the tensors without a
+    gradient (img [3,H,W], depth_map [H*W] or None, n_pix, n_rays, width, height, seed,
+    seed_counter, shift_first, flags, descs).  Returns (c2w [4,4], world [1,4,4], ray_idx [R],
+    pixels [1,R,2], rgb_gt [1,R,3], cam, ray, view, ray_norm, d_src, mask)."""
+    r, t, init = pose if pose is not None else (None, None, None)
+    sc, sh = aff if aff is not None else (None, None)
+    return _StepHead.apply(r, t, init, c2w_in, K, scale_mat, sc, sh, a)
 
 
 # ------------------------------------------------------------------ loss terms

@@ -196,18 +196,22 @@ class Renderer(nn.Module):
         return torch.norm(normals[:n] - normals[n:], dim=-1)
 
     def nope_nerf(self, pixels, depth, camera_mat, world_mat, scale_mat, add_noise=False, it=100000,
-                  eval_=False, noise=None, dense_depth=False, normal_noise=None, field_grad=True):
+                  eval_=False, noise=None, dense_depth=False, normal_noise=None, field_grad=True, rays=None):
         """rendering.py:36-168.  Extra keyword arguments of the MI355X build:
         ``noise`` injects the stratified U[0,1) tensor (1,R,S) instead of torch.rand;
         ``dense_depth`` returns unmasked depth_pred/depth_gt plus 'depth_mask' (R,) so the
         training step never needs the boolean-index host sync (rendering.py:151-153);
         ``normal_noise`` injects the (N,3) jitter of the normal_loss branch;
         ``field_grad=False`` renders a frozen field: gradients reach the camera matrices only
-        and no field parameter gets a ``.grad`` (Trainer_pose, eval_pose_one_epoch.py:44-61)."""
+        and no field parameter gets a ``.grad`` (Trainer_pose, eval_pose_one_epoch.py:44-61);
+        ``rays`` = (cam, ray, view, ray_norm, d_src, mask) of these pixels, built by the caller
+        (the Trainer's step head) instead of the two launches below."""
         cfg = self.cfg
         S = cfg["num_points"] - cfg.get("outside_steps", 0)
         near, far = float(self.depth_range[0]), float(self.depth_range[1])
-        if pixels.is_cuda:       # two launches: the unprojection matrix, then every ray
+        if rays is not None:
+            cam, ray, view, ray_norm, d_src, mask = rays
+        elif pixels.is_cuda:     # two launches: the unprojection matrix, then every ray
             M = unproject_matrix(camera_mat, world_mat, scale_mat)
             cam, ray, view, ray_norm, d_src, mask = camera_rays_hip(
                 M, pixels, depth, cfg["normalise_ray"], view_ones=not cfg["use_ray_dir"])

@@ -23,7 +23,8 @@ import torch.distributed as dist
 from torch.nn import functional as F
 
 from .common import arange_pixels, get_tensor_values, inv, project_to_cam, transform_to_world
-from .rays import can_sample_on_device, depth_affine, mat4_mul
+from .rays import can_sample_on_device, depth_affine, mat4_mul, step_head, step_head_enabled
+from . import _hip
 from .rays import sample_rays as sample_rays_dev
 from .losses import Loss
 from .pair import pair_losses
@@ -333,6 +334,64 @@ class Trainer(object):
                     ray_idx, p, rgb_gt = draw()
         return ray_idx, p, rgb_gt
 
+    # ------------------------------------------------------------------ step head
+    def _step_head_applies(self, img, depth_input, depth_mask, need_valid):
+        """Whether this step's head runs as the single nerf_step_head launch: NERF_STEP_HEAD not 0,
+        one image on the GPU that the device sampler can draw from, no injected draw, an H x W
+        depth prior that is data, a LearnPose (or no) pose net with a fixed init_c2w, and an
+        all-invalid draw ruled out on the host (graph mode's rule)."""
+        if not step_head_enabled() or self.inject is not None or self.rendering_technique != "nope_nerf":
+            return False
+        B, _, h, w = img.shape
+        if not (img.is_cuda and B == 1 and can_sample_on_device(h * w, self.n_training_points)):
+            return False
+        if not (depth_input.is_cuda and tuple(depth_input.shape[-2:]) == (h, w) and depth_input.numel() == h * w
+                and not depth_input.requires_grad):
+            return False
+        net = self.pose_param_net
+        if net is not None and not (hasattr(net, "r") and hasattr(net, "t") and hasattr(net, "init_c2w")
+                                    and (net.init_c2w is None or not net.init_c2w.requires_grad)):
+            return False
+        rcfg = getattr(getattr(self.model, "renderer", None), "cfg", None)
+        if rcfg is None or "normalise_ray" not in rcfg or "use_ray_dir" not in rcfg:
+            return False
+        if need_valid and depth_mask is not None:
+            if depth_mask.is_cuda:
+                return False
+            n_pix = h * w
+            n_invalid = n_pix - int(depth_mask.sum())
+            if n_invalid > 0 and (n_invalid / n_pix) ** self.n_training_points > 1e-9:
+                return False
+        return True
+
+    def _step_head(self, img, depth_input, img_idx, pose_gt, camera_mat, scale_mat, aff):
+        """The head of the step in one launch (rays.step_head): returns (c2w, world_mat [1,4,4],
+        ray_idx, pixels, rgb_gt, rays) with rays = (cam, ray, view, ray_norm, d_src, mask) for
+        Renderer.nope_nerf; the field runner's weights are packed by the same launch and marked so."""
+        _, _, h, w = img.shape
+        if self.seed_counter is not None:      # graph-capture mode: see sample_rays
+            seed = (0x2545F4914F6CDD1D + self.rank * 0x632BE59BD9B4E019) & 0xFFFFFFFFFFFFFFFF
+        else:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) + self.rank * 0x632BE59BD9B4E019
+        net = self.pose_param_net
+        pose = c2w_in = None
+        if net is not None:
+            cam = int(img_idx)
+            pose = (net.r[cam], net.t[cam], None if net.init_c2w is None else net.init_c2w[cam])
+        else:
+            c2w_in = pose_gt.reshape(4, 4)
+        rcfg = self.model.renderer.cfg
+        flags = (_hip.RAYS_NORMALISE if rcfg["normalise_ray"] else 0) | (0 if rcfg["use_ray_dir"] else _hip.RAYS_VIEW_ONES)
+        runner = self._field_runner()
+        descs = runner.pack_descs() if runner is not None else ()
+        a = {"img": img[0], "depth_map": depth_input.reshape(-1), "n_pix": h * w, "n_rays": self.n_training_points,
+             "width": w, "height": h, "seed": seed, "seed_counter": self.seed_counter,
+             "shift_first": self.shift_first, "flags": flags, "descs": descs}
+        c2w, world_mat, ray_idx, p, rgb_gt, *rays = step_head(pose, c2w_in, camera_mat, scale_mat, aff, a)
+        if runner is not None:
+            runner.prepacked = True
+        return c2w, world_mat, ray_idx, p, rgb_gt, tuple(rays)
+
     # ------------------------------------------------------------------ loss
     def compute_loss(self, data, eval_mode=False, it=None, epoch=None, scheduling_start=None,
                      out_render_path=None):
@@ -358,8 +417,9 @@ class Trainer(object):
         # the ground-truth relative pose only feeds the t-cycle term (losses.py:161-162)
         world_mat_gt = inv(pose_gt).unsqueeze(0) if (use_ref_imgs and weights["t_cycle_weight"] != 0.0) else None
         num_cams = self.pose_param_net.num_cams if self.pose_param_net is not None else None
-        c2w = self.pose_param_net(img_idx) if self.pose_param_net is not None else pose_gt.reshape(4, 4)
-        world_mat = inv(c2w).unsqueeze(0)
+        # the step head (one launch for the pose, the inverse, the draw, the gathers, the camera
+        # rays and the field's weight pack) where it applies; today's launches everywhere else
+        head = render_model and self._step_head_applies(img, depth_input, depth_mask, data.get("img.dpt") is None)
         scale_input = shift_input = None
         affine_in = None
         if self.distortion_net is not None:
@@ -381,6 +441,14 @@ class Trainer(object):
             camera_mat = torch.cat([fxfy[0:1], pad, -fxfy[1:2], pad, -one, pad, one]).view(1, 4, 4)
         else:
             camera_mat = camera_mat_gt
+        if head and self.distortion_net is not None and (affine_in is None or scale_input.numel() != 1
+                                                         or shift_input.numel() != 1):
+            head = False                    # a dense or non-scalar distortion: the separate launches
+        if head:
+            c2w = world_mat = None          # both come out of the step head below
+        else:
+            c2w = self.pose_param_net(img_idx) if self.pose_param_net is not None else pose_gt.reshape(4, 4)
+            world_mat = inv(c2w).unsqueeze(0)
 
         extra = {}
         if self.inject is not None:
@@ -389,15 +457,25 @@ class Trainer(object):
             rgb_gt = img.view(B, 3, h * w).permute(0, 2, 1)[:, ray_idx]
             p = self._pixels(h, w, dev)[:, ray_idx]
             extra["noise"] = noise.to(dev)
+        elif head:
+            aff = (scale_input, shift_input) if affine_in is not None else None
+            c2w, world_mat, ray_idx, p, rgb_gt, extra["rays"] = self._step_head(
+                img, depth_input, img_idx, pose_gt, camera_mat, scale_mat, aff)
         else:
             ray_idx, p, rgb_gt = self.sample_rays(h * w, depth_mask, data.get("img.dpt") is None, img=img,
                                                   hw=(h, w))
 
         rendered_rgb = rendered_depth = gt_depth = dmask = None
         if render_model:
-            out = self.model(p, ray_idx, camera_mat, world_mat, scale_mat, self.rendering_technique, it=it,
-                             eval_mode=eval_mode, depth_img=depth_input, img_size=(h, w), depth_affine=affine_in,
-                             dense_depth=not eval_mode, **extra)
+            try:
+                out = self.model(p, ray_idx, camera_mat, world_mat, scale_mat, self.rendering_technique, it=it,
+                                 eval_mode=eval_mode, depth_img=depth_input, img_size=(h, w), depth_affine=affine_in,
+                                 dense_depth=not eval_mode, **extra)
+            finally:
+                if head:        # the one-shot mark never outlives the render it was set for
+                    runner = self._field_runner()
+                    if runner is not None:
+                        runner.prepacked = False
             rendered_rgb, rendered_depth, gt_depth = out["rgb"], out["depth_pred"], out["depth_gt"]
             dmask = out.get("depth_mask")
 
