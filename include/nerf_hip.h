@@ -45,7 +45,7 @@ extern "C" {
  * 15 the chain images' compact exponent arrays (nerf_pack_desc dst_cs / dst_cts) and
  * nerf_linear_bwd_weight_job_groups.  Additive within 15 (no existing signature changed): the
  * frozen-field entries, nerf_image_metrics(_workspace_bytes) and nerf_pair_forward_ssim /
- * nerf_pair_backward_ssim. */
+ * nerf_pair_backward_ssim, nerf_pair_backward_cam. */
 #define NERF_HIP_ABI_VERSION 15
 int nerf_hip_abi_version(void);
 const char* nerf_hip_last_error(void);
@@ -764,6 +764,24 @@ int nerf_pair_backward_ssim(const float* d1, const float* d2, int h, int w, cons
                             int rgbs_detach_scale, const float* work, const int* nn, const float* samples,
                             const float* out3, const float* go_pc, const float* go_rgbs, float* gXY,
                             float* g_d1, float* g_d2, float* g13, float* part13, void* stream);
+/* The backward with a learned camera matrix (pose.learn_focal; training.py:266-273, 361-376,
+ * common.py:436-457): the arguments of nerf_pair_backward_ssim, samples == NULL selecting the plain
+ * rgb_s term of nerf_pair_backward and a non-NULL samples the with_ssim one.  g_d1, g_d2 and g13 are
+ * those entries' outputs bit for bit; gK16 [16] (required) is the gradient of go_pc loss_pc +
+ * go_rgbs loss_rgb_s w.r.t. K taken as an unconstrained row-major 4 x 4 leaf, which enters through
+ * inv(K) in both point clouds and directly in the projection h3 = K[:3] [q, 1]:
+ *   gK = sum over points of -a1 b1^T - a2 b2^T + [gh (x) [q, 1]; 0],
+ *   a = inv(K)^T[:, :3] g (g the gradient arriving at pc1 / pc2), b = inv(K) [x d, y d, d, 1],
+ * the projection term from the points whose sample carries rgb_s gradient (the valid ones on the
+ * plain path, every one with_ssim); a clamped point's q = (nl, nl, nl) gives R, t and the depths
+ * nothing but its projection still depends on K, as in torch autograd.  Formed per point and summed
+ * in fixed order (bit-repeatable).
+ * part29: scratch [29 * ceil(P / 256)] floats ({R, t, s1, K} per block) in place of part13. */
+int nerf_pair_backward_cam(const float* d1, const float* d2, int h, int w, const float* K, const float* Rt,
+                           const float* s1, float nl, const float* img1, const float* img2,
+                           int rgbs_detach_scale, const float* work, const int* nn, const float* samples,
+                           const float* out3, const float* go_pc, const float* go_rgbs, float* gXY,
+                           float* g_d1, float* g_d2, float* g13, float* gK16, float* part29, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Windowed image metrics of the novel-view evaluation (metrics.hip; model/eval_images.py:94-97:

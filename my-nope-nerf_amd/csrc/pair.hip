@@ -19,6 +19,10 @@
 // img1 / img2 samples, k_pair_ssim (one more launch forward) forms the 3 x 3 windows and the
 // blended partials from them, and the backward's per-point kernel gathers d rgb_s / d sample
 // from the saved samples of columns c-2 .. c+2 of its row (no launch more, no atomics).
+//
+// A learned camera matrix (pose.learn_focal; nerf_pair_backward_cam): the backward's per-point kernel
+// also forms the point's 16 terms of d/dK (K through inv(K) in both point clouds and directly in the
+// projection) and the reduction carries 29 partials per workgroup instead of 13 (no launch more).
 #include "common.hpp"
 #include "mat4.hpp"
 
@@ -119,6 +123,20 @@ __device__ __forceinline__ Reproj reproject(const PairArgs& a, const PairConst& 
 }
 
 constexpr int PT = 256;   // threads per point-kernel workgroup
+
+// v, as a value the compiler knows nothing about
+__device__ __forceinline__ float opaque(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ int opaque(int v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ const float* opaque(const float* p) {
+    asm volatile("" : "+s"(p));
+    return p;
+}
 
 // the workgroup's {sum, count} of the rgb_s term, waves added in order
 __device__ __forceinline__ void pair_block_partials(float s, float n, float (*red)[2], float* __restrict__ rgbs_part) {
@@ -481,12 +499,53 @@ __device__ __forceinline__ float pair_scattered(const unsigned long long* s, int
     return (float)((double)(long long)s[k] * (g / fix));
 }
 
+// d rgb_s / d p_re of point i (times g), as k_pair_bwd_points forms it inline for an unclamped point;
+// the CAM kernels call this for the clamped ones
+template <bool SSIM>
+__device__ __forceinline__ void pair_sample_grad(const PairArgs& a, const PairConst& m, const float* __restrict__ samp,
+                                                 int i, float x, float y, const Reproj& r, float g, float& gpx,
+                                                 float& gpy) {
+    const int hw = a.h * a.w;
+    gpx = 0.f;
+    gpy = 0.f;
+    if constexpr (SSIM) {
+        float gv[3];
+        ssim_grad_rgb2(a, m, samp, i, r.valid, g, gv);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float dpx, dpy;
+            bilinear_pad(a.img2 + c * hw, a.h, a.w, r.px, r.py, &dpx, &dpy);
+            gpx += gv[c] * dpx;
+            gpy += gv[c] * dpy;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v1 = bilinear(a.img1 + c * hw, a.h, a.w, x, y);
+            float dpx, dpy;
+            const float v2 = bilinear(a.img2 + c * hw, a.h, a.w, r.px, r.py, &dpx, &dpy);
+            const float e = v1 - v2;
+            const float gv2 = (fabsf(e) <= 1.f) ? -g * (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) : 0.f;
+            gpx += gv2 * dpx;
+            gpy += gv2 * dpy;
+        }
+    }
+}
+
 // per point: the direct chamfer terms plus the scattered ones -> dX_i, dY_i; the rgb_s term
 // -> d pc1_rot; then d1 / d2 gradients and the R, t, scale partials of the workgroup
 // (part[block][13] = {R (9), t (3), s1})
 // SSIM: the rgb_s term is the with_ssim one, its gradient gathered from the saved samples `samp`;
 // every unclamped point takes part, valid or not
-template <bool SSIM>
+// CAM: also the gradient w.r.t. the camera matrix as an unconstrained 4 x 4 leaf (a learned focal,
+// intrinsics.py), part[block][29] = {R, t, s1, gK (16, row-major)}.  K enters twice.  Through the
+// unprojection pc = (inv(K) v)[:3], v = [x d, y d, d, 1]: d inv(K) = -inv(K) dK inv(K), so a point
+// with gradient g at pc gives -a b^T, a = inv(K)^T[:, :3] g, b = inv(K) v (pc1 and pc2, g the whole
+// of what arrives: chamfer own + scattered terms and, unless detached, the reprojection).  Through
+// the projection h3 = K[:3] [q, 1]: gh (x) [q, 1] on rows 0-2.  The 16 products are formed per point
+// and summed over points (not sum g v^T transformed afterwards: that sum's rounding is not bounded
+// by sum_p |gK_p|); each is reduced as soon as it is formed, so no 16 more registers stay live.
+template <bool SSIM, bool CAM = false>
 __global__ __launch_bounds__(PT) void k_pair_bwd_points(PairArgs a, const float* __restrict__ X,
                                                         const float* __restrict__ Y, const int* __restrict__ nn,
                                                         const float* __restrict__ go_pc,
@@ -496,10 +555,13 @@ __global__ __launch_bounds__(PT) void k_pair_bwd_points(PairArgs a, const float*
                                                         const unsigned long long* __restrict__ gY,
                                                         float* __restrict__ g_d1, float* __restrict__ g_d2,
                                                         float* __restrict__ part, const float* __restrict__ samp) {
-    __shared__ float red[PT / 64][13];
+    constexpr int NA = CAM ? 29 : 13;
+    __shared__ float red[PT / 64][NA];
     const int i = blockIdx.x * PT + threadIdx.x;
     const int P = a.P;
     float acc[13];
+    // CAM: a, b of pc1 and pc2, gh and q of the projection (0 for a point that takes no part)
+    float ca[2][4] = {}, cb[2][4] = {}, cgh[3] = {0.f, 0.f, 0.f}, cq[3] = {0.f, 0.f, 0.f}, cgp[2] = {0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 13; ++k) acc[k] = 0.f;
     if (i < P) {
@@ -595,6 +657,7 @@ __global__ __launch_bounds__(PT) void k_pair_bwd_points(PairArgs a, const float*
                 float gq[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) gq[c] = gh[0] * m.K[c] + gh[1] * m.K[4 + c] + gh[2] * m.K[8 + c];
+                if constexpr (CAM) { cgp[0] = gpx; cgp[1] = gpy; }
                 // q = R pc1 + t
 #pragma unroll
                 for (int rr = 0; rr < 3; ++rr) {
@@ -616,17 +679,78 @@ __global__ __launch_bounds__(PT) void k_pair_bwd_points(PairArgs a, const float*
         for (int r = 0; r < 3; ++r) u[r] = m.Kinv[4 * r] * x + m.Kinv[4 * r + 1] * y + m.Kinv[4 * r + 2];
         if (g_d1) g_d1[i] = gpc1[0] * u[0] + gpc1[1] * u[1] + gpc1[2] * u[2];
         if (g_d2) g_d2[i] = gpc2[0] * u[0] + gpc2[1] * u[1] + gpc2[2] * u[2];
+        if constexpr (CAM) {
+            // The camera terms, on opaque copies of what the code above produced (gpc1, gpc2, the sample
+            // gradient of an unclamped point) and on its inputs read again through opaque pointers.  The
+            // compiler must not see common subexpressions between the two: merged, its vectoriser pairs
+            // and contracts the operations above differently, and g_d1, g_d2, g13 would no longer be the
+            // fixed-camera kernel's bits (the same operations, rounded elsewhere).
+            PairArgs ao = a;
+            ao.d1 = opaque(a.d1); ao.d2 = opaque(a.d2); ao.Kg = opaque(a.Kg); ao.Rtg = opaque(a.Rtg);
+            ao.img1 = opaque(a.img1); ao.img2 = opaque(a.img2);
+            ao.s1g = nullptr;      // the scale does not enter: the gradients arrive at pc1, pc2 themselves
+            const float* sampo = opaque(samp);
+            const int io = opaque(i);
+            PairConst mc;
+            mc.load(ao);
+            float xo, yo, gg[2][3], pp[2][3];
+            pc_pixel(io, a.h, a.w, xo, yo);
+            const float dd[2] = {ao.d1[io], ao.d2[io]};
+            unproject_pt(mc.Kinv, xo, yo, dd[0], pp[0]);      // pc1, pc2: the bits above (no contraction)
+            unproject_pt(mc.Kinv, xo, yo, dd[1], pp[1]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { gg[0][k] = opaque(gpc1[k]); gg[1][k] = opaque(gpc2[k]); }
+            // the projection's term gh (x) [q, 1].  A clamped point's q = (nl, nl, nl) is a constant and
+            // gives R, t and pc1 nothing, but its projection K[:3] [q, 1] still depends on K: its sample
+            // gradient is formed here
+            if (a.img1 != nullptr && go_rgbs != nullptr && red_out[2] > 0.f) {
+                const Reproj r = reproject(ao, mc, pp[0]);
+                if (SSIM || r.valid) {
+                    float gpx = opaque(cgp[0]), gpy = opaque(cgp[1]);
+                    if (r.bad) pair_sample_grad<SSIM>(ao, mc, sampo, io, xo, yo, r, *go_rgbs / red_out[2], gpx, gpy);
+                    const float iz = 1.f / r.h3[2];
+                    cgh[0] = gpx * iz;
+                    cgh[1] = gpy * iz;
+                    cgh[2] = -(gpx * r.px + gpy * r.py) * iz;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) cq[c] = r.q[c];
+                }
+            }
+            // the unprojections' terms -a b^T
+#pragma unroll
+            for (int z = 0; z < 2; ++z) {
+                const float* g = gg[z];
+                const float d = dd[z];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ca[z][j] = mc.Kinv[j] * g[0] + mc.Kinv[4 + j] * g[1] + mc.Kinv[8 + j] * g[2];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) cb[z][k] = pp[z][k];
+                cb[z][3] = ((mc.Kinv[12] * (xo * d) + mc.Kinv[13] * (yo * d)) + mc.Kinv[14] * d) + mc.Kinv[15];
+            }
+        }
     }
 #pragma unroll
     for (int k = 0; k < 13; ++k) {
         const float s = wave_sum(acc[k]);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
     }
+    if constexpr (CAM) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float v = -(ca[0][j] * cb[0][k] + ca[1][j] * cb[1][k]);
+                if (j < 3) v += cgh[j] * (k < 3 ? cq[k] : 1.f);
+                const float s = wave_sum(v);
+                if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][13 + 4 * j + k] = s;
+            }
+        }
+    }
     __syncthreads();
-    if (threadIdx.x < 13) {
+    if (threadIdx.x < NA) {
         float s = 0.f;
         for (int wv = 0; wv < PT / 64; ++wv) s += red[wv][threadIdx.x];
-        part[13 * blockIdx.x + threadIdx.x] = s;
+        part[NA * blockIdx.x + threadIdx.x] = s;
     }
 }
 
@@ -637,6 +761,17 @@ __global__ __launch_bounds__(64) void k_pair_bwd_reduce(const float* __restrict_
     float s = 0.f;
     for (int b = 0; b < nblk; ++b) s += part[13 * b + k];
     out13[k] = s;
+}
+
+// the 29-wide partials of the CAM kernel: g13 as k_pair_bwd_reduce sums it, and gK16
+__global__ __launch_bounds__(64) void k_pair_bwd_reduce_cam(const float* __restrict__ part, int nblk,
+                                                            float* __restrict__ out13, float* __restrict__ gK16) {
+    const int k = threadIdx.x;
+    if (k >= 29) return;
+    float s = 0.f;
+    for (int b = 0; b < nblk; ++b) s += part[29 * b + k];
+    if (k < 13) out13[k] = s;
+    else gK16[k - 13] = s;
 }
 
 }  // namespace nerf
@@ -721,12 +856,14 @@ static int pair_backward_impl(const char* fn, const float* d1, const float* d2, 
                               const float* Rt16, const float* s1, float nl, const float* img1, const float* img2,
                               int rgbs_detach_scale, const float* work, const int* nn, const float* samples, bool ssim,
                               const float* out3, const float* go_pc, const float* go_rgbs, float* gXY, float* g_d1,
-                              float* g_d2, float* g13, float* part13, void* stream) {
+                              float* g_d2, float* g13, float* part13, void* stream, float* gK16 = nullptr,
+                              bool cam = false) {
     PairArgs a;
     const int rc = fill_args(a, d1, d2, h, w, K16, Rt16, s1, nl, img1, img2, rgbs_detach_scale);
     if (rc != NERF_OK) return rc;
     NERF_CHECK_PTR(work); NERF_CHECK_PTR(nn); NERF_CHECK_PTR(out3); NERF_CHECK_PTR(gXY); NERF_CHECK_PTR(g13);
     NERF_CHECK_PTR(part13);
+    if (cam) NERF_CHECK_PTR(gK16);
     if (ssim) {
         NERF_CHECK(img1 != nullptr, "%s: the SSIM term needs img1 and img2", fn);
         NERF_CHECK(samples != nullptr, "%s: samples is NULL ([2][P][3] floats)", fn);
@@ -741,6 +878,17 @@ static int pair_backward_impl(const char* fn, const float* d1, const float* d2, 
     hipStream_t s = as_stream(stream);
     (void)hipMemsetAsync(gXY, 0, 6 * (size_t)P * sizeof(unsigned long long), s);
     if (go_pc != nullptr) hipLaunchKernelGGL(k_pair_bwd_scatter, dim3(nb), dim3(PT), 0, s, X, Y, P, nn, gX, gY);
+    if (cam) {     // part13 holds 29 floats per block here
+        if (ssim)
+            hipLaunchKernelGGL((k_pair_bwd_points<true, true>), dim3(nb), dim3(PT), 0, s, a, X, Y, nn, go_pc, go_rgbs, out3,
+                               (const unsigned long long*)gX, (const unsigned long long*)gY, g_d1, g_d2, part13, samples);
+        else
+            hipLaunchKernelGGL((k_pair_bwd_points<false, true>), dim3(nb), dim3(PT), 0, s, a, X, Y, nn, go_pc, go_rgbs, out3,
+                               (const unsigned long long*)gX, (const unsigned long long*)gY, g_d1, g_d2, part13,
+                               (const float*)nullptr);
+        hipLaunchKernelGGL(k_pair_bwd_reduce_cam, dim3(1), dim3(64), 0, s, (const float*)part13, nb, g13, gK16);
+        return check_launch(fn);
+    }
     if (ssim)
         hipLaunchKernelGGL(k_pair_bwd_points<true>, dim3(nb), dim3(PT), 0, s, a, X, Y, nn, go_pc, go_rgbs, out3,
                            (const unsigned long long*)gX, (const unsigned long long*)gY, g_d1, g_d2, part13, samples);
@@ -769,4 +917,14 @@ extern "C" int nerf_pair_backward_ssim(const float* d1, const float* d2, int h, 
                                        float* part13, void* stream) {
     return pair_backward_impl(__func__, d1, d2, h, w, K16, Rt16, s1, nl, img1, img2, rgbs_detach_scale, work, nn, samples,
                               true, out3, go_pc, go_rgbs, gXY, g_d1, g_d2, g13, part13, stream);
+}
+
+extern "C" int nerf_pair_backward_cam(const float* d1, const float* d2, int h, int w, const float* K16,
+                                      const float* Rt16, const float* s1, float nl, const float* img1,
+                                      const float* img2, int rgbs_detach_scale, const float* work, const int* nn,
+                                      const float* samples, const float* out3, const float* go_pc,
+                                      const float* go_rgbs, float* gXY, float* g_d1, float* g_d2, float* g13,
+                                      float* gK16, float* part29, void* stream) {
+    return pair_backward_impl(__func__, d1, d2, h, w, K16, Rt16, s1, nl, img1, img2, rgbs_detach_scale, work, nn, samples,
+                              samples != nullptr, out3, go_pc, go_rgbs, gXY, g_d1, g_d2, g13, part29, stream, gK16, true);
 }

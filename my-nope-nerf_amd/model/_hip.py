@@ -188,6 +188,8 @@ _SIGS = {
                                 _c_p], _c_i),
     "nerf_pair_backward_ssim": ([_c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p,
                                  _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_pair_backward_cam": ([_c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p,
+                                _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_image_metrics_workspace_bytes": ([_c_i, _c_i, _c_i, _c_i], ctypes.c_size_t),
     "nerf_image_metrics": ([_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i, _c_i,
                             _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p], _c_i),
@@ -631,6 +633,15 @@ def pair_backward_ssim(d1, d2, h, w, K, Rt, s1, nl, img1, img2, rgbs_detach_scal
     _call("nerf_pair_backward_ssim", _ptr(d1), _ptr(d2), int(h), int(w), _ptr(K), _ptr(Rt), _ptr(s1), float(nl),
           _ptr(img1), _ptr(img2), int(rgbs_detach_scale), _ptr(work), _ptr(nn), _ptr(samples), _ptr(out3),
           _ptr(go_pc), _ptr(go_rgbs), _ptr(gxy), _ptr(g_d1), _ptr(g_d2), _ptr(g13), _ptr(part13), _stream())
+
+
+def pair_backward_cam(d1, d2, h, w, K, Rt, s1, nl, img1, img2, rgbs_detach_scale, work, nn, samples, out3, go_pc,
+                      go_rgbs, gxy, g_d1, g_d2, g13, gK16, part29):
+    """The pair backward with the camera-matrix gradient gK16 [16] (a learned focal); samples None: the plain
+    rgb_s term, else the with_ssim one; part29: 29 floats per 256-point block."""
+    _call("nerf_pair_backward_cam", _ptr(d1), _ptr(d2), int(h), int(w), _ptr(K), _ptr(Rt), _ptr(s1), float(nl),
+          _ptr(img1), _ptr(img2), int(rgbs_detach_scale), _ptr(work), _ptr(nn), _ptr(samples), _ptr(out3),
+          _ptr(go_pc), _ptr(go_rgbs), _ptr(gxy), _ptr(g_d1), _ptr(g_d2), _ptr(g13), _ptr(gK16), _ptr(part29), _stream())
 
 
 def image_metrics_workspace_bytes(batch, channels, height, width) -> int:

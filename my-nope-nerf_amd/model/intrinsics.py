@@ -2,7 +2,8 @@
 drivers construct when ``pose.learn_focal`` is set (train.py:140, vis/render.py:78).
 
 Never learned in the V_KITTI configs, so it stays a host-side torch
-module; a learned K also makes the Trainer keep the torch pair terms (training.py).
+module; the camera matrix the Trainer builds from it gets its gradient from the HIP kernels
+(nerf_unproject_matrix_bwd on the ray side, nerf_pair_backward_cam for the image-pair terms).
 Parameterisation: order 2 stores a with fx = a**2, order 1 stores fx itself."""
 from __future__ import annotations
 

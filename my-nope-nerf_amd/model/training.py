@@ -543,14 +543,16 @@ class Trainer(object):
             d1, d2 = a1(d1, nl), a2(d2, nl)
         else:
             d1, d2 = d1.clamp_min(nl), d2.clamp_min(nl)
-        if img.is_cuda and not camera_mat.requires_grad and self.match_method == "dense":
-            # pair.hip: point clouds, chamfer and reprojection terms in 4 + 4 launches (5 + 4 with_ssim)
+        if img.is_cuda and self.match_method == "dense":
+            # pair.hip: point clouds, chamfer and reprojection terms in 4 + 4 launches (5 + 4 with_ssim);
+            # a learned focal (camera_mat requires grad) gets its gradient from the same launches
             want_rgbs = weights["rgb_s_weight"] != 0.0
             i1 = F.interpolate(img1, res, mode="bilinear") if want_rgbs else None
             i2 = F.interpolate(img2, res, mode="bilinear") if want_rgbs else None
             s = scale1 if (self.scale_pcs and scale1 is not None) else None
             l_pc, l_rgbs = pair_losses(d1, d2, camera_mat, Rt_rel_12, s, i1, i2, res, nl, self.detach_rgbs_scale,
-                                       with_ssim=bool(self.loss.cfg.get("with_ssim", False)))
+                                       with_ssim=bool(self.loss.cfg.get("with_ssim", False)),
+                                       camera_grad=camera_mat.requires_grad)
             return {"pair_losses": (l_pc, l_rgbs), "sample_resolution": res, "rt_12": Rt_rel_12,
                     "rt_12_gt": Rt_rel_12_gt}
         R_rel_12, t_rel_12 = Rt_rel_12[:, :3, :3], Rt_rel_12[:, :3, 3]
