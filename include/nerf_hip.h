@@ -591,6 +591,28 @@ int nerf_sample_rays(int n_pix, int n_rays, uint64_t seed, int width, int height
  * counter at c the key words are xored with the low and the high half of
  * (c + 1) * 0x9E3779B97F4A7C15 mod 2^64. */
 
+/* nerf_sample_rays_valid (additive entry, ABI version unchanged): the reference's "draw again
+ * until a drawn ray has a valid depth" loop (training.py:275-283, `while not m[ray_idx].any()`,
+ * over img.depth_mask of the sparse depth priors) inside the launch, so the step never waits for
+ * the host.  The arguments are nerf_sample_rays' plus valid [n_pix] (u8, non-zero = the pixel has
+ * a depth) and attempts (optional, device int).
+ *   The attempt rule: attempt a = 0, 1, ... is nerf_sample_rays' draw rule, unchanged, under the
+ *   seed seed_a = (seed + a * 0xD1B54A32D192ED03) mod 2^64 -- the key is the two halves of seed_a,
+ *   then mixed with seed_counter as above; the Philox counters stay (slot, round, 0x5a4d, 0) and
+ *   the hash set is cleared per attempt.  Attempt 0 is nerf_sample_rays' draw bit for bit.  An
+ *   attempt is accepted when any drawn index v has valid[v] != 0 (one OR over the workgroup).  The
+ *   gathers run once, on the accepted attempt; seed_counter advances by one per launch whatever
+ *   the number of attempts.  attempts receives the 1-based number of the accepted attempt; status
+ *   is that attempt's.
+ *   Deviation from the reference: with no valid pixel at all the reference loops for ever; here,
+ *   after NERF_SAMPLE_MAX_ATTEMPTS attempts without a valid pixel, attempts is 0 and the outputs
+ *   hold the last attempt's draw.
+ *   valid == NULL: every attempt is accepted -- nerf_sample_rays exactly (attempts = 1). */
+#define NERF_SAMPLE_MAX_ATTEMPTS 64
+int nerf_sample_rays_valid(int n_pix, int n_rays, uint64_t seed, int width, int height, const float* img,
+                           const uint8_t* valid, int64_t* idx, float* pixels, float* rgb, int* status,
+                           int* attempts, uint64_t* seed_counter, void* stream);
+
 /* Batched 4x4 inverse (torch.inverse / linalg.inv_ex, common.py:139-141, training.py:255-257):
  * Gauss-Jordan with partial pivoting, a [n][4][4] -> out [n][4][4]. */
 int nerf_mat4_inv(const float* a, int n, float* out, void* stream);
@@ -701,6 +723,13 @@ typedef struct {
     uint8_t* mask;           /* [n_rays], optional */
 } nerf_step_head_rays;
 int nerf_step_head(const nerf_step_head_rays* rays, const nerf_pack_desc* descs, int n_desc, void* stream);
+/* The step head with nerf_sample_rays_valid's attempt loop around its draw stage (additive entry):
+ * valid [n_pix] and attempts as there (both need rays); every later stage runs once, on the
+ * accepted attempt, and every result is bit for bit that of nerf_sample_rays_valid and the other
+ * separate entries.  With valid == NULL and attempts == NULL this launches nerf_step_head's own
+ * kernel: the loop is a separate instantiation and costs the path without a mask nothing. */
+int nerf_step_head_valid(const nerf_step_head_rays* rays, const uint8_t* valid, int* attempts,
+                         const nerf_pack_desc* descs, int n_desc, void* stream);
 
 /* Loss.forward's render terms (losses.py:28-33, 60-66, 195-228), four device scalars:
  * total = w_rgb l_rgb + w_depth l_depth, l_rgb = sum|e| or sum e^2 over rgb [R][3] / R,
@@ -718,6 +747,31 @@ int nerf_ray_loss_bwd(const float* rgb, const float* rgb_gt, int n_rays, const f
                       float w_depth, const float* go_total, const float* go_rgb, const float* go_depth,
                       const float* go_l2, const float* cnt, float* g_rgb, float* g_depth_pred,
                       float* g_depth_gt, void* stream);
+
+/* nerf_ray_loss with depth_loss_type 'invariant' (losses.py:35-58 depth_loss_dpt through
+ * get_depth_loss :67-68; additive entries): l_rgb, l2_mean and total as nerf_ray_loss; over the
+ * masked entries of depth_pred / depth_gt (mask NULL = all n_depth, both required),
+ *   t = torch.median(d) -- the lower middle value, 0-based rank (cnt - 1) / 2, selected exactly
+ *   (a radix select on order-preserving keys) --, s = mean |d - t|,
+ *   l_depth = mean(((p - t_p) / s_p - (g - t_g) / s_g)^2).
+ * stats (device, 8 floats) = {cnt, t_p, s_p, t_g, s_g, entries equal to t_p, entries equal to
+ * t_g, 0}: what the backward reads instead of selecting again.  One workgroup, sums in f64 in a
+ * fixed order (deterministic).  Requires n_depth <= NERF_SAMPLE_MAX_RAYS.  Inputs under the mask
+ * must be finite.  cnt = 0, cnt = 1 or all masked values equal give s = 0 and a NaN l_depth and
+ * total, as the reference's expressions do.
+ * Backward: the gradients torch autograd gives for these expressions -- the median's gradient is
+ * spread evenly over the entries equal to it, d|x|/dx at 0 is 0; entries outside the mask get 0;
+ * where s = 0 every masked entry is NaN; g_rgb does not depend on the depth term.  Each of g_rgb,
+ * g_depth_pred, g_depth_gt is optional (g_depth_gt NULL: detach_gt_depth). */
+int nerf_ray_loss_invariant(const float* rgb, const float* rgb_gt, int n_rays, const float* depth_pred,
+                            const float* depth_gt, const uint8_t* mask, int n_depth, int rgb_l1, float w_rgb,
+                            float w_depth, float* total, float* l_rgb, float* l_depth, float* l2_mean,
+                            float* stats, void* stream);
+int nerf_ray_loss_invariant_bwd(const float* rgb, const float* rgb_gt, int n_rays, const float* depth_pred,
+                                const float* depth_gt, const uint8_t* mask, int n_depth, int rgb_l1, float w_rgb,
+                                float w_depth, const float* go_total, const float* go_rgb, const float* go_depth,
+                                const float* go_l2, const float* stats, float* g_rgb, float* g_depth_pred,
+                                float* g_depth_gt, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Image-pair terms of the full step (pair.hip; training.py:359-405, losses.py:116-159):

@@ -10,7 +10,11 @@
 //   * k_camera_rays   : origin, unit direction, |P1 - o|, d_src and the depth mask per ray
 //                       (rendering.py:52-80) and its backward (pose / distortion learning);
 //   * k_ray_loss(_bwd): rgb l1/l2 + masked depth l1 + l2_mean and their gradients
-//                       (losses.py:28-33, 60-66, 164-228).
+//                       (losses.py:28-33, 60-66, 164-228);
+//   * k_sample_rays_valid: the draw repeated until a drawn pixel has a valid depth
+//                       (training.py:275-283's host loop over img.depth_mask, inside the launch);
+//   * k_ray_loss_inv(_bwd): the same with depth_loss_type 'invariant' (losses.py:35-58): both
+//                       medians selected in the launch, no boolean indexing, no host sync.
 // All are launch-latency bound (a few KB per step); the point is the launch count.
 #include "common.hpp"
 #include "mat4.hpp"
@@ -38,6 +42,40 @@ __global__ __launch_bounds__(SR_THREADS) void k_sample_rays(int n_pix, int R, ui
     bool pend[SR_PER_THREAD];
     const int st = sample_draw<SR_THREADS>(n_pix, R, key, table, owner, SR_LOG_TABLE, val, pend);
     if (tid == 0 && status != nullptr) *status = st;   // rounds used, 0 = gave up
+#pragma unroll
+    for (int q = 0; q < SR_PER_THREAD; ++q) {
+        const int j = tid + q * SR_THREADS;
+        if (j >= R) continue;
+        float px, py;
+        sample_gather(j, pend[q] ? 0u : val[q], width, height, img, idx, pix, rgb, px, py);
+    }
+    if (ctr != nullptr) {
+        __syncthreads();
+        if (tid == 0) *ctr = c + 1;
+    }
+}
+
+// k_sample_rays with the draw repeated until a drawn pixel has a valid depth (rays_dev.hpp
+// sample_draw_valid); the gathers run once, on the accepted (or last) attempt.
+__global__ __launch_bounds__(SR_THREADS) void k_sample_rays_valid(int n_pix, int R, unsigned long long seed,
+                                                                  int width, int height,
+                                                                  const float* __restrict__ img,
+                                                                  const uint8_t* __restrict__ valid,
+                                                                  int64_t* __restrict__ idx, float* __restrict__ pix,
+                                                                  float* __restrict__ rgb, int* __restrict__ status,
+                                                                  int* __restrict__ attempts,
+                                                                  unsigned long long* __restrict__ ctr) {
+    __shared__ uint32_t table[SR_TABLE];
+    __shared__ uint32_t owner[SR_TABLE];
+    const int tid = threadIdx.x;
+    const unsigned long long c = ctr ? *ctr : 0ull;
+    uint32_t val[SR_PER_THREAD];
+    bool pend[SR_PER_THREAD];
+    int att;
+    const int st = sample_draw_valid<SR_THREADS>(n_pix, R, seed, ctr != nullptr, c, valid, table, owner,
+                                                 SR_LOG_TABLE, val, pend, att);
+    if (tid == 0 && status != nullptr) *status = st;
+    if (tid == 0 && attempts != nullptr) *attempts = att;
 #pragma unroll
     for (int q = 0; q < SR_PER_THREAD; ++q) {
         const int j = tid + q * SR_THREADS;
@@ -468,6 +506,226 @@ __global__ void k_ray_loss_bwd(const float* __restrict__ rgb, const float* __res
     }
 }
 
+// ------------------------------------------------------------------------------------
+// depth_loss_type 'invariant' (losses.py:35-58 through get_depth_loss :67-68) beside the rgb terms
+// of k_ray_loss: over the masked entries, t = torch.median (the value of 0-based rank (cnt - 1) / 2),
+// s = mean |d - t| for the prediction and the prior, l_depth = mean(((p - t_p) / s_p - (g - t_g) / s_g)^2).
+// One workgroup; thread tid holds entries tid + q LI_THREADS in registers.  The median is a
+// radix select on order-preserving keys, most significant bit first, one block-wide count per bit
+// for both medians at once -- exact, whatever the values.  The depth arithmetic and its sums run in
+// f64 in a fixed order (per-thread, wave butterfly, 16 wave sums in order): deterministic.
+constexpr int LI_THREADS = 1024, LI_PER = NERF_SAMPLE_MAX_RAYS / LI_THREADS, LI_WAVES = LI_THREADS / 64;
+
+__device__ __forceinline__ uint32_t float_key(float x) {     // a < b  <=>  key(a) < key(b), finite a, b
+    const uint32_t b = __float_as_uint(x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_float(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// the sums of v[0..N) over the workgroup, the same bits in every thread; red: [LI_WAVES][N]
+template <int N>
+__device__ __forceinline__ void block_sum_d(double (&v)[N], double* red) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = wave_sum_d(v[i]);
+    __syncthreads();   // the readers of an earlier use of red are done
+    if (lane == 0)
+#pragma unroll
+        for (int i = 0; i < N; ++i) red[wv * N + i] = v[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double s = 0.0;
+        for (int w = 0; w < LI_WAVES; ++w) s += red[w * N + i];
+        v[i] = s;
+    }
+}
+
+// stats = {cnt, t_p, s_p, t_g, s_g, entries equal to t_p, entries equal to t_g, 0} (s_p, s_g: for the caller)
+__global__ __launch_bounds__(LI_THREADS) void k_ray_loss_inv(const float* __restrict__ rgb,
+                                                             const float* __restrict__ gt, int R,
+                                                             const float* __restrict__ dp,
+                                                             const float* __restrict__ dg,
+                                                             const uint8_t* __restrict__ mask, int M, int l1,
+                                                             float w_rgb, float w_depth, float* __restrict__ total,
+                                                             float* __restrict__ l_rgb, float* __restrict__ l_depth,
+                                                             float* __restrict__ l2_mean,
+                                                             float* __restrict__ stats) {
+    __shared__ float red[LI_WAVES][2];
+    __shared__ int cred[2][LI_WAVES];
+    __shared__ double dred[LI_WAVES * 4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    // the rgb sums, as k_ray_loss takes them
+    float s2 = 0.f, s1 = 0.f;
+    for (int i = tid; i < 3 * R; i += LI_THREADS) {
+        const float e = rgb[i] - gt[i];
+        s2 += e * e;
+        s1 += fabsf(e);
+    }
+    s2 = wave_sum(s2); s1 = wave_sum(s1);
+    if (lane == 0) { red[wv][0] = s2; red[wv][1] = s1; }
+    float p[LI_PER], g[LI_PER];
+    uint32_t kp[LI_PER], kg[LI_PER];
+    bool m[LI_PER];
+    int mine = 0;
+#pragma unroll
+    for (int q = 0; q < LI_PER; ++q) {
+        const int i = tid + q * LI_THREADS;
+        m[q] = i < M && (mask == nullptr || mask[i] != 0);
+        p[q] = m[q] ? dp[i] : 0.f;
+        g[q] = m[q] ? dg[i] : 0.f;
+        kp[q] = float_key(p[q]);
+        kg[q] = float_key(g[q]);
+        mine += m[q] ? 1 : 0;
+    }
+    double c1[1] = {(double)mine};
+    block_sum_d<1>(c1, dred);          // its barriers also publish red
+    const int cnt = (int)c1[0];
+    // rank (cnt - 1) / 2 of both key sets: bit by bit, the count of keys that share the prefix so
+    // far and have a 0 next (the two counts packed in one int: each is at most 4096)
+    uint32_t pre_p = 0u, pre_g = 0u;
+    int rk_p = (cnt - 1) / 2, rk_g = rk_p;
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t above = ~((2u << bit) - 1u);   // the bits above `bit` (0 at bit 31)
+        int c0 = 0;
+#pragma unroll
+        for (int q = 0; q < LI_PER; ++q) {
+            if (!m[q]) continue;
+            c0 += ((kp[q] & above) == pre_p && !((kp[q] >> bit) & 1u)) ? 1 : 0;
+            c0 += ((kg[q] & above) == pre_g && !((kg[q] >> bit) & 1u)) ? 65536 : 0;
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) c0 += __shfl_xor(c0, off, 64);
+        int* cr = cred[bit & 1];       // two buffers: one barrier per bit
+        if (lane == 0) cr[wv] = c0;
+        __syncthreads();
+        int n0 = 0;
+        for (int w = 0; w < LI_WAVES; ++w) n0 += cr[w];
+        const int n0p = n0 & 0xffff, n0g = n0 >> 16;
+        if (rk_p >= n0p) { rk_p -= n0p; pre_p |= 1u << bit; }
+        if (rk_g >= n0g) { rk_g -= n0g; pre_g |= 1u << bit; }
+    }
+    const float t_p = key_float(pre_p), t_g = key_float(pre_g);   // cnt = 0: all ones, a NaN
+    double ep[LI_PER], eg[LI_PER], v4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < LI_PER; ++q) {
+        ep[q] = (double)p[q] - (double)t_p;
+        eg[q] = (double)g[q] - (double)t_g;
+        if (!m[q]) continue;
+        v4[0] += fabs(ep[q]);
+        v4[1] += fabs(eg[q]);
+        v4[2] += p[q] == t_p ? 1.0 : 0.0;
+        v4[3] += g[q] == t_g ? 1.0 : 0.0;
+    }
+    block_sum_d<4>(v4, dred);
+    const double s_p = v4[0] / (double)cnt, s_g = v4[1] / (double)cnt;   // 0 / 0 with no entry
+    double sq[1] = {0.0};
+#pragma unroll
+    for (int q = 0; q < LI_PER; ++q) {
+        if (!m[q]) continue;
+        const double r = ep[q] / s_p - eg[q] / s_g;
+        sq[0] += r * r;
+    }
+    block_sum_d<1>(sq, dred);
+    if (tid == 0) {
+        float a = 0.f, b = 0.f;
+        for (int w = 0; w < LI_WAVES; ++w) { a += red[w][0]; b += red[w][1]; }
+        const float lr = (l1 ? b : a) / (float)R;
+        const float ld = (float)(sq[0] / (double)cnt);
+        *l_rgb = lr;
+        *l_depth = ld;
+        *l2_mean = a / (float)(3 * R);
+        *total = w_rgb * lr + w_depth * ld;
+        stats[0] = (float)cnt; stats[1] = t_p; stats[2] = (float)s_p; stats[3] = t_g; stats[4] = (float)s_g;
+        stats[5] = (float)v4[2]; stats[6] = (float)v4[3]; stats[7] = 0.f;
+    }
+}
+
+// Its backward, what torch autograd gives for the expressions above: with u = (p - t_p) / s_p,
+// v = (g - t_g) / s_g, a_i = a_dep 2 (u_i - v_i) / cnt, A = sum a, B_p = sum a u, B_g = sum a v,
+// S = sum sign(d - t) and m_j = [d_j == t] / ties (the median's gradient, spread evenly over the
+// entries equal to it; sign(0) = 0):
+//   g_p[j] = (a_j - A m_j - B_p (sign_j - S_p m_j) / cnt) / s_p
+//   g_g[j] = (-a_j + A m'_j + B_g (sign'_j - S_g m'_j) / cnt) / s_g
+// Entries outside the mask get 0; without go_total and go_depth every depth gradient is 0.
+// s = 0 (cnt <= 1, or all entries equal) gives NaN on every masked entry, as autograd does.
+__global__ __launch_bounds__(LI_THREADS) void k_ray_loss_inv_bwd(
+    const float* __restrict__ rgb, const float* __restrict__ gt, int R, const float* __restrict__ dp,
+    const float* __restrict__ dg, const uint8_t* __restrict__ mask, int M, int l1, float w_rgb, float w_depth,
+    const float* __restrict__ go_total, const float* __restrict__ go_rgb, const float* __restrict__ go_depth,
+    const float* __restrict__ go_l2, const float* __restrict__ stats, float* __restrict__ g_rgb,
+    float* __restrict__ g_dp, float* __restrict__ g_dg) {
+    __shared__ double dred[LI_WAVES * 5];
+    const int tid = threadIdx.x;
+    const float gt_ = go_total ? *go_total : 0.f;
+    const float a_rgb = gt_ * w_rgb + (go_rgb ? *go_rgb : 0.f);
+    const float a_dep = gt_ * w_depth + (go_depth ? *go_depth : 0.f);
+    const float a_l2 = go_l2 ? *go_l2 : 0.f;
+    if (g_rgb != nullptr)
+        for (int i = tid; i < 3 * R; i += LI_THREADS) {
+            const float e = rgb[i] - gt[i];
+            const float dl = l1 ? (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) : 2.f * e;
+            g_rgb[i] = a_rgb * dl / (float)R + a_l2 * (2.f * e) / (float)(3 * R);
+        }
+    if (g_dp == nullptr && g_dg == nullptr) return;
+    if (go_total == nullptr && go_depth == nullptr) {      // l_depth reaches no upstream scalar
+        for (int i = tid; i < M; i += LI_THREADS) {
+            if (g_dp) g_dp[i] = 0.f;
+            if (g_dg) g_dg[i] = 0.f;
+        }
+        return;
+    }
+    // the count, the medians and their tie counts come from the forward; s is summed again from them, in
+    // the forward's order, so that it is the forward's f64 value and not its f32 copy in stats
+    const double cnt = stats[0], t_p = stats[1], t_g = stats[3], ties_p = stats[5], ties_g = stats[6];
+    bool m[LI_PER];
+    double ep[LI_PER], eg[LI_PER], a[LI_PER], v2[2] = {0.0, 0.0}, v5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    auto sgn = [](double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0); };
+#pragma unroll
+    for (int q = 0; q < LI_PER; ++q) {
+        const int i = tid + q * LI_THREADS;
+        m[q] = i < M && (mask == nullptr || mask[i] != 0);
+        ep[q] = m[q] ? (double)dp[i] - t_p : 0.0;
+        eg[q] = m[q] ? (double)dg[i] - t_g : 0.0;
+        v2[0] += fabs(ep[q]);
+        v2[1] += fabs(eg[q]);
+    }
+    block_sum_d<2>(v2, dred);
+    const double s_p = v2[0] / cnt, s_g = v2[1] / cnt;
+#pragma unroll
+    for (int q = 0; q < LI_PER; ++q) {
+        a[q] = 0.0;
+        if (!m[q]) continue;
+        const double u = ep[q] / s_p, v = eg[q] / s_g;
+        a[q] = (double)a_dep * 2.0 * (u - v) / cnt;
+        v5[0] += a[q];
+        v5[1] += a[q] * u;
+        v5[2] += a[q] * v;
+        v5[3] += sgn(ep[q]);
+        v5[4] += sgn(eg[q]);
+    }
+    block_sum_d<5>(v5, dred);
+#pragma unroll
+    for (int q = 0; q < LI_PER; ++q) {
+        const int i = tid + q * LI_THREADS;
+        if (i >= M) continue;
+        float gp = 0.f, gg = 0.f;
+        if (m[q]) {
+            const double mp = ep[q] == 0.0 ? 1.0 / ties_p : 0.0, mg = eg[q] == 0.0 ? 1.0 / ties_g : 0.0;
+            gp = (float)((a[q] - v5[0] * mp - v5[1] * (sgn(ep[q]) - v5[3] * mp) / cnt) / s_p);
+            gg = (float)((-a[q] + v5[0] * mg + v5[2] * (sgn(eg[q]) - v5[4] * mg) / cnt) / s_g);
+        }
+        if (g_dp) g_dp[i] = gp;
+        if (g_dg) g_dg[i] = gg;
+    }
+}
+
 }  // namespace nerf
 
 using namespace nerf;
@@ -487,6 +745,28 @@ extern "C" int nerf_sample_rays(int n_pix, int n_rays, uint64_t seed, int width,
     const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
     hipLaunchKernelGGL(k_sample_rays, dim3(1), dim3(SR_THREADS), 0, as_stream(stream), n_pix, n_rays, key,
                        width, height, img, idx, pixels, rgb, status,
+                       reinterpret_cast<unsigned long long*>(seed_counter));
+    return check_launch(__func__);
+}
+
+extern "C" int nerf_sample_rays_valid(int n_pix, int n_rays, uint64_t seed, int width, int height,
+                                      const float* img, const uint8_t* valid, int64_t* idx, float* pixels,
+                                      float* rgb, int* status, int* attempts, uint64_t* seed_counter,
+                                      void* stream) {
+    if (valid == nullptr && attempts == nullptr)      // no mask, nothing to report: today's launch
+        return nerf_sample_rays(n_pix, n_rays, seed, width, height, img, idx, pixels, rgb, status, seed_counter,
+                                stream);
+    NERF_CHECK_PTR(idx);
+    NERF_CHECK(n_rays > 0 && n_rays <= NERF_SAMPLE_MAX_RAYS, "%s: n_rays=%d outside 1..%d", __func__, n_rays,
+               NERF_SAMPLE_MAX_RAYS);
+    NERF_CHECK(n_pix >= 2 * n_rays, "%s: n_pix=%d < 2*n_rays=%d (draw a permutation instead)", __func__, n_pix,
+               2 * n_rays);
+    NERF_CHECK(pixels == nullptr || (width > 1 && height > 1 && width * height == n_pix),
+               "%s: pixels need width, height > 1 with width*height == n_pix", __func__);
+    NERF_CHECK(rgb == nullptr || (img != nullptr && width * height == n_pix), "%s: rgb needs img [3][n_pix]",
+               __func__);
+    hipLaunchKernelGGL(k_sample_rays_valid, dim3(1), dim3(SR_THREADS), 0, as_stream(stream), n_pix, n_rays,
+                       (unsigned long long)seed, width, height, img, valid, idx, pixels, rgb, status, attempts,
                        reinterpret_cast<unsigned long long*>(seed_counter));
     return check_launch(__func__);
 }
@@ -619,5 +899,38 @@ extern "C" int nerf_ray_loss_bwd(const float* rgb, const float* rgb_gt, int n_ra
     hipLaunchKernelGGL(k_ray_loss_bwd, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), rgb, rgb_gt, n_rays,
                        depth_pred, depth_gt, mask, n_depth, rgb_l1, w_rgb, w_depth, go_total, go_rgb, go_depth,
                        go_l2, cnt, g_rgb, g_depth_pred, g_depth_gt);
+    return check_launch(__func__);
+}
+
+extern "C" int nerf_ray_loss_invariant(const float* rgb, const float* rgb_gt, int n_rays, const float* depth_pred,
+                                       const float* depth_gt, const uint8_t* mask, int n_depth, int rgb_l1,
+                                       float w_rgb, float w_depth, float* total, float* l_rgb, float* l_depth,
+                                       float* l2_mean, float* stats, void* stream) {
+    NERF_CHECK_PTR(rgb); NERF_CHECK_PTR(rgb_gt); NERF_CHECK_PTR(depth_pred); NERF_CHECK_PTR(depth_gt);
+    NERF_CHECK_PTR(total); NERF_CHECK_PTR(l_rgb); NERF_CHECK_PTR(l_depth); NERF_CHECK_PTR(l2_mean);
+    NERF_CHECK_PTR(stats);
+    NERF_CHECK(n_rays > 0, "%s: n_rays=%d", __func__, n_rays);
+    NERF_CHECK(n_depth >= 0 && n_depth <= NERF_SAMPLE_MAX_RAYS, "%s: n_depth=%d outside 0..%d", __func__, n_depth,
+               NERF_SAMPLE_MAX_RAYS);
+    hipLaunchKernelGGL(k_ray_loss_inv, dim3(1), dim3(LI_THREADS), 0, as_stream(stream), rgb, rgb_gt, n_rays,
+                       depth_pred, depth_gt, mask, n_depth, rgb_l1, w_rgb, w_depth, total, l_rgb, l_depth, l2_mean,
+                       stats);
+    return check_launch(__func__);
+}
+
+extern "C" int nerf_ray_loss_invariant_bwd(const float* rgb, const float* rgb_gt, int n_rays,
+                                           const float* depth_pred, const float* depth_gt, const uint8_t* mask,
+                                           int n_depth, int rgb_l1, float w_rgb, float w_depth,
+                                           const float* go_total, const float* go_rgb, const float* go_depth,
+                                           const float* go_l2, const float* stats, float* g_rgb,
+                                           float* g_depth_pred, float* g_depth_gt, void* stream) {
+    NERF_CHECK_PTR(rgb); NERF_CHECK_PTR(rgb_gt); NERF_CHECK_PTR(depth_pred); NERF_CHECK_PTR(depth_gt);
+    NERF_CHECK_PTR(stats);
+    NERF_CHECK(n_rays > 0, "%s: n_rays=%d", __func__, n_rays);
+    NERF_CHECK(n_depth >= 0 && n_depth <= NERF_SAMPLE_MAX_RAYS, "%s: n_depth=%d outside 0..%d", __func__, n_depth,
+               NERF_SAMPLE_MAX_RAYS);
+    hipLaunchKernelGGL(k_ray_loss_inv_bwd, dim3(1), dim3(LI_THREADS), 0, as_stream(stream), rgb, rgb_gt, n_rays,
+                       depth_pred, depth_gt, mask, n_depth, rgb_l1, w_rgb, w_depth, go_total, go_rgb, go_depth,
+                       go_l2, stats, g_rgb, g_depth_pred, g_depth_gt);
     return check_launch(__func__);
 }

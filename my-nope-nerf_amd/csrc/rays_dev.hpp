@@ -101,6 +101,41 @@ __device__ __forceinline__ int sample_draw(int n_pix, int R, uint2 key, uint32_t
     return done ? round + 1 : 0;
 }
 
+// Draw until a drawn pixel has a valid depth (training.py:275-283's `while not m[ray_idx].any()`):
+// attempt a = 0, 1, ... is sample_draw with the seed seed + a SR_ATTEMPT_STEP (mod 2^64), its key
+// mixed with the device counter as ever, the hash set cleared per attempt (sample_draw clears it).
+// An attempt is accepted when any drawn index v has valid[v] != 0 (valid == NULL: always) -- one
+// block-wide OR, so every thread leaves the loop in the same attempt.  Returns the status word of
+// the accepted (or last) attempt; attempts = its 1-based number, 0 when none of
+// NERF_SAMPLE_MAX_ATTEMPTS was accepted (val / pend then hold the last attempt's draw).
+constexpr unsigned long long SR_ATTEMPT_STEP = 0xD1B54A32D192ED03ull;
+template <int THREADS>
+__device__ __forceinline__ int sample_draw_valid(int n_pix, int R, unsigned long long seed, bool has_ctr,
+                                                 unsigned long long c, const uint8_t* __restrict__ valid,
+                                                 uint32_t* table, uint32_t* owner, int log_table,
+                                                 uint32_t (&val)[NERF_SAMPLE_MAX_RAYS / THREADS],
+                                                 bool (&pend)[NERF_SAMPLE_MAX_RAYS / THREADS], int& attempts) {
+    constexpr int PER = NERF_SAMPLE_MAX_RAYS / THREADS;
+    const int tid = threadIdx.x;
+    int st = 0;
+    attempts = 0;
+    for (int a = 0; a < NERF_SAMPLE_MAX_ATTEMPTS; ++a) {
+        const unsigned long long sa = seed + (unsigned long long)a * SR_ATTEMPT_STEP;
+        uint2 key = make_uint2((uint32_t)sa, (uint32_t)(sa >> 32));
+        if (has_ctr) key = sample_key_mix(key, c);
+        st = sample_draw<THREADS>(n_pix, R, key, table, owner, log_table, val, pend);
+        int hit = valid == nullptr;
+#pragma unroll
+        for (int q = 0; q < PER; ++q)
+            if (!hit && tid + q * THREADS < R && valid[pend[q] ? 0u : val[q]] != 0) hit = 1;
+        if (__syncthreads_or(hit)) {   // uniform: the OR is the same in every thread
+            attempts = a + 1;
+            break;
+        }
+    }
+    return st;
+}
+
 // the pixel and colour gathers of ray slot j at pixel index v (common.py:36-39, training.py:284-287)
 __device__ __forceinline__ void sample_gather(int j, uint32_t v, int width, int height,
                                               const float* __restrict__ img, int64_t* __restrict__ idx,

@@ -28,8 +28,12 @@ struct StepHeadArgs {
     int pack_blocks;   // blocks per descriptor: SH_F32 (+ SH_H with fp16 pair images)
 };
 
+// VALID: the draw repeats until a drawn pixel has a valid depth (rays_dev.hpp sample_draw_valid);
+// the instantiation without it is the kernel as it was.
+template <bool VALID>
 __device__ __forceinline__ void ray_block(const nerf_step_head_rays& a, uint32_t* table, uint32_t* owner,
-                                          int log_table) {
+                                          int log_table, const uint8_t* __restrict__ valid,
+                                          int* __restrict__ attempts) {
     __shared__ float Ms[16];
     const int tid = threadIdx.x;
     const int R = a.n_rays;
@@ -53,11 +57,19 @@ __device__ __forceinline__ void ray_block(const nerf_step_head_rays& a, uint32_t
     // device step counter: read by all threads, advanced once at the end (k_sample_rays' rule)
     unsigned long long* ctr = reinterpret_cast<unsigned long long*>(a.seed_counter);
     const unsigned long long c = ctr ? *ctr : 0ull;
-    uint2 key = make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-    if (ctr) key = sample_key_mix(key, c);
     uint32_t val[SH_PER_THREAD];
     bool pend[SH_PER_THREAD];
-    const int st = sample_draw<SH_THREADS>(a.n_pix, R, key, table, owner, log_table, val, pend);   // syncs: Ms is visible
+    int st;
+    if constexpr (VALID) {
+        int att;
+        st = sample_draw_valid<SH_THREADS>(a.n_pix, R, a.seed, ctr != nullptr, c, valid, table, owner, log_table,
+                                           val, pend, att);
+        if (tid == 0 && attempts != nullptr) *attempts = att;
+    } else {
+        uint2 key = make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+        if (ctr) key = sample_key_mix(key, c);
+        st = sample_draw<SH_THREADS>(a.n_pix, R, key, table, owner, log_table, val, pend);   // syncs: Ms is visible
+    }
     if (tid == 0 && a.status != nullptr) *a.status = st;
     float M[16];
 #pragma unroll
@@ -89,12 +101,14 @@ __device__ __forceinline__ void ray_block(const nerf_step_head_rays& a, uint32_t
     }
 }
 
-__global__ __launch_bounds__(SH_THREADS) void k_step_head(StepHeadArgs a, PackBatch pb) {
+template <bool VALID>
+__device__ __forceinline__ void step_head_body(const StepHeadArgs& a, const PackBatch& pb, const uint8_t* valid,
+                                               int* attempts) {
     extern __shared__ uint32_t sh_table[];
     int b = blockIdx.x;
     if (a.has_rays) {
         if (b == 0) {
-            ray_block(a.rays, sh_table, sh_table + (1 << a.log_table), a.log_table);
+            ray_block<VALID>(a.rays, sh_table, sh_table + (1 << a.log_table), a.log_table, valid, attempts);
             return;
         }
         --b;
@@ -105,33 +119,43 @@ __global__ __launch_bounds__(SH_THREADS) void k_step_head(StepHeadArgs a, PackBa
     else pack_h(d, bx - SH_F32, SH_H);
 }
 
+__global__ __launch_bounds__(SH_THREADS) void k_step_head(StepHeadArgs a, PackBatch pb) {
+    step_head_body<false>(a, pb, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(SH_THREADS) void k_step_head_valid(StepHeadArgs a, PackBatch pb,
+                                                                const uint8_t* __restrict__ valid,
+                                                                int* __restrict__ attempts) {
+    step_head_body<true>(a, pb, valid, attempts);
+}
+
 }  // namespace nerf
 
 using namespace nerf;
 
-extern "C" int nerf_step_head(const nerf_step_head_rays* rays, const nerf_pack_desc* descs, int n_desc,
-                              void* stream) {
-    NERF_CHECK(rays != nullptr || n_desc > 0, "%s: neither a ray block nor pack descriptors", __func__);
-    NERF_CHECK(n_desc >= 0 && n_desc <= NERF_MAX_PACK, "%s: n_desc=%d outside 0..%d", __func__, n_desc,
+static int step_head_launch(const char* fn, const nerf_step_head_rays* rays, const uint8_t* valid,
+                            int* attempts, bool with_valid, const nerf_pack_desc* descs, int n_desc, void* stream) {
+    NERF_CHECK(rays != nullptr || n_desc > 0, "%s: neither a ray block nor pack descriptors", fn);
+    NERF_CHECK(n_desc >= 0 && n_desc <= NERF_MAX_PACK, "%s: n_desc=%d outside 0..%d", fn, n_desc,
                NERF_MAX_PACK);
-    NERF_CHECK(n_desc == 0 || descs != nullptr, "%s: null pointer 'descs'", __func__);
+    NERF_CHECK(n_desc == 0 || descs != nullptr, "%s: null pointer 'descs'", fn);
     StepHeadArgs a{};
     size_t lds = 0;
     if (rays != nullptr) {
         const nerf_step_head_rays& r = *rays;
-        NERF_CHECK(r.n_rays > 0 && r.n_rays <= NERF_SAMPLE_MAX_RAYS, "%s: n_rays=%d outside 1..%d", __func__,
+        NERF_CHECK(r.n_rays > 0 && r.n_rays <= NERF_SAMPLE_MAX_RAYS, "%s: n_rays=%d outside 1..%d", fn,
                    r.n_rays, NERF_SAMPLE_MAX_RAYS);
-        NERF_CHECK(r.n_pix >= 2 * r.n_rays, "%s: n_pix=%d < 2*n_rays=%d (draw a permutation instead)", __func__,
+        NERF_CHECK(r.n_pix >= 2 * r.n_rays, "%s: n_pix=%d < 2*n_rays=%d (draw a permutation instead)", fn,
                    r.n_pix, 2 * r.n_rays);
         NERF_CHECK(r.width > 1 && r.height > 1 && r.width * r.height == r.n_pix,
-                   "%s: width, height > 1 with width*height == n_pix", __func__);
+                   "%s: width, height > 1 with width*height == n_pix", fn);
         NERF_CHECK((r.r != nullptr && r.t != nullptr) || (r.r == nullptr && r.c2w_in != nullptr),
-                   "%s: the pose is (r, t) or c2w_in", __func__);
+                   "%s: the pose is (r, t) or c2w_in", fn);
         NERF_CHECK(r.K != nullptr && r.scale != nullptr && r.img != nullptr, "%s: null pointer among K, scale, img",
-                   __func__);
+                   fn);
         NERF_CHECK(r.aff_scale == nullptr || (r.aff_shift != nullptr && r.depth_map != nullptr),
-                   "%s: aff_scale needs aff_shift and depth_map", __func__);
-#define SH_OUT(p) NERF_CHECK(r.p != nullptr, "%s: null output '%s'", __func__, #p)
+                   "%s: aff_scale needs aff_shift and depth_map", fn);
+#define SH_OUT(p) NERF_CHECK(r.p != nullptr, "%s: null output '%s'", fn, #p)
         SH_OUT(c2w); SH_OUT(world); SH_OUT(M); SH_OUT(inverses); SH_OUT(idx); SH_OUT(pixels); SH_OUT(rgb);
         SH_OUT(cam); SH_OUT(ray); SH_OUT(ray_norm); SH_OUT(d_src);
         if (r.depth_map != nullptr) SH_OUT(depth_g);
@@ -147,14 +171,40 @@ extern "C" int nerf_step_head(const nerf_step_head_rays* rays, const nerf_pack_d
     PackBatch pb{};
     bool images = false;
     if (n_desc > 0)
-        if (const int rc = pack_batch_fill(__func__, descs, n_desc, pb, images)) return rc;
+        if (const int rc = pack_batch_fill(fn, descs, n_desc, pb, images)) return rc;
     a.pack_blocks = SH_F32 + ((pb.f16 && images) ? SH_H : 0);
-    if (lds > 64 * 1024) {   // the largest tables (n_rays > 2048) need the per-kernel opt-in
+    const unsigned grid = (unsigned)(a.has_rays + n_desc * a.pack_blocks);
+    if (with_valid) {
+        if (lds > 64 * 1024) {   // the largest tables (n_rays > 2048) need the per-kernel opt-in
+            static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step_head_valid),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                               128 * 1024);
+            (void)once;
+        }
+        hipLaunchKernelGGL(k_step_head_valid, dim3(grid), dim3(SH_THREADS), lds, as_stream(stream), a, pb, valid,
+                           attempts);
+        return check_launch(fn);
+    }
+    if (lds > 64 * 1024) {
         static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step_head),
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)once;
     }
-    const unsigned grid = (unsigned)(a.has_rays + n_desc * a.pack_blocks);
     hipLaunchKernelGGL(k_step_head, dim3(grid), dim3(SH_THREADS), lds, as_stream(stream), a, pb);
-    return check_launch(__func__);
+    return check_launch(fn);
+}
+
+extern "C" int nerf_step_head(const nerf_step_head_rays* rays, const nerf_pack_desc* descs, int n_desc,
+                              void* stream) {
+    return step_head_launch(__func__, rays, nullptr, nullptr, false, descs, n_desc, stream);
+}
+
+// The step head with the draw repeated until a drawn pixel has a valid depth.  valid == NULL and
+// attempts == NULL: nerf_step_head's own kernel.
+extern "C" int nerf_step_head_valid(const nerf_step_head_rays* rays, const uint8_t* valid, int* attempts,
+                                    const nerf_pack_desc* descs, int n_desc, void* stream) {
+    NERF_CHECK((valid == nullptr && attempts == nullptr) || rays != nullptr, "%s: valid / attempts without rays",
+               __func__);
+    return step_head_launch(__func__, rays, valid, attempts, valid != nullptr || attempts != nullptr, descs, n_desc,
+                            stream);
 }

@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("NERF_HIP_LIB", os.path.join(_HERE, "..", "lib", "libn
 
 ROW_TILE = 128
 SAMPLE_MAX_RAYS = 4096      # NERF_SAMPLE_MAX_RAYS
+SAMPLE_MAX_ATTEMPTS = 64    # NERF_SAMPLE_MAX_ATTEMPTS
 RAYS_NORMALISE = 1          # NERF_RAYS_NORMALISE
 RAYS_VIEW_ONES = 2          # NERF_RAYS_VIEW_ONES
 ENC_P = 64
@@ -163,6 +164,8 @@ _SIGS = {
     "nerf_gemm_debug_ablate": ([_c_i], _c_i),
     "nerf_gemm_debug_stamps": ([_c_p], _c_i),
     "nerf_sample_rays": ([_c_i, _c_i, ctypes.c_uint64, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_sample_rays_valid": ([_c_i, _c_i, ctypes.c_uint64, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                _c_p], _c_i),
     "nerf_mat4_inv": ([_c_p, _c_i, _c_p, _c_p], _c_i),
     "nerf_pose_c2w": ([_c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_unproject_matrix": ([_c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
@@ -176,6 +179,11 @@ _SIGS = {
     "nerf_camera_rays": ([_c_p, _c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_camera_rays_bwd": ([_c_p, _c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_step_head": ([ctypes.POINTER(StepHeadRays), ctypes.POINTER(PackDesc), _c_i, _c_p], _c_i),
+    "nerf_step_head_valid": ([ctypes.POINTER(StepHeadRays), _c_p, _c_p, ctypes.POINTER(PackDesc), _c_i, _c_p], _c_i),
+    "nerf_ray_loss_invariant": ([_c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_i, _c_i, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p,
+                                 _c_p, _c_p], _c_i),
+    "nerf_ray_loss_invariant_bwd": ([_c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_i, _c_i, _c_f, _c_f, _c_p, _c_p, _c_p,
+                                     _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_ray_loss": ([_c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_i, _c_i, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p,
                        _c_p], _c_i),
     "nerf_ray_loss_bwd": ([_c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_i, _c_i, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p,
@@ -522,6 +530,19 @@ def sample_rays(n_pix, n_rays, seed, width, height, img, idx, pixels=None, rgb=N
           _ptr(img), _ptr(idx), _ptr(pixels), _ptr(rgb), _ptr(status), _ptr(seed_counter), _stream())
 
 
+def sample_rays_valid(n_pix, n_rays, seed, width, height, img, valid, idx, pixels=None, rgb=None, status=None,
+                      attempts=None, seed_counter=None):
+    """sample_rays drawing until a drawn pixel has valid[v] != 0 (valid: device uint8 / bool [n_pix] or
+    None); attempts: optional device int32 [1], the 1-based attempt accepted (0: none of 64)."""
+    if valid is not None and (valid.numel() != int(n_pix) or valid.dtype not in (torch.uint8, torch.bool)):
+        raise ValueError("sample_rays_valid: valid must be uint8 / bool [n_pix]")
+    if attempts is not None and attempts.dtype != torch.int32:
+        raise ValueError("sample_rays_valid: attempts must be int32")
+    _call("nerf_sample_rays_valid", int(n_pix), int(n_rays), int(seed) & 0xFFFFFFFFFFFFFFFF, int(width), int(height),
+          _ptr(img), _ptr(valid), _ptr(idx), _ptr(pixels), _ptr(rgb), _ptr(status), _ptr(attempts), _ptr(seed_counter),
+          _stream())
+
+
 def mat4_inv(a, out):
     _call("nerf_mat4_inv", _ptr(a), a.numel() // 16, _ptr(out), _stream())
 
@@ -582,6 +603,16 @@ def step_head(rays: Optional[StepHeadRays], descs: Sequence[PackDesc] = ()):
     _call("nerf_step_head", None if rays is None else ctypes.byref(rays), arr, len(descs), _stream())
 
 
+def step_head_valid(rays: StepHeadRays, valid, attempts=None, descs: Sequence[PackDesc] = ()):
+    """step_head with the draw repeated until a drawn pixel has valid[v] != 0 (see sample_rays_valid)."""
+    if valid is not None and (valid.numel() != rays.n_pix or valid.dtype not in (torch.uint8, torch.bool)):
+        raise ValueError("step_head_valid: valid must be uint8 / bool [n_pix]")
+    if attempts is not None and attempts.dtype != torch.int32:
+        raise ValueError("step_head_valid: attempts must be int32")
+    arr = (PackDesc * len(descs))(*descs) if len(descs) else None
+    _call("nerf_step_head_valid", ctypes.byref(rays), _ptr(valid), _ptr(attempts), arr, len(descs), _stream())
+
+
 def step_head_rays(**kw) -> StepHeadRays:
     """StepHeadRays from keyword arguments: tensors become checked device pointers."""
     return StepHeadRays(**{k: (_ptr(v) if isinstance(v, torch.Tensor) else v) for k, v in kw.items()
@@ -599,6 +630,23 @@ def ray_loss_bwd(rgb, rgb_gt, n_rays, depth_pred, depth_gt, mask, n_depth, rgb_l
     """go: four upstream scalars (total, l_rgb, l_depth, l2_mean), each a device tensor or None."""
     _call("nerf_ray_loss_bwd", _ptr(rgb), _ptr(rgb_gt), int(n_rays), _ptr(depth_pred), _ptr(depth_gt),
           _ptr(mask), int(n_depth), int(rgb_l1), float(w_rgb), float(w_depth), *[_ptr(g) for g in go], _ptr(cnt),
+          _ptr(g_rgb), _ptr(g_dp), _ptr(g_dg), _stream())
+
+
+def ray_loss_invariant(rgb, rgb_gt, n_rays, depth_pred, depth_gt, mask, n_depth, rgb_l1, w_rgb, w_depth, out, stats):
+    """out: four device scalars (total, l_rgb, l_depth, l2_mean); stats: device float32 [8]."""
+    if stats.numel() < 8 or stats.dtype != torch.float32:
+        raise ValueError("ray_loss_invariant: stats needs 8 float32 slots")
+    _call("nerf_ray_loss_invariant", _ptr(rgb), _ptr(rgb_gt), int(n_rays), _ptr(depth_pred), _ptr(depth_gt),
+          _ptr(mask), int(n_depth), int(rgb_l1), float(w_rgb), float(w_depth), *[_ptr(o) for o in out], _ptr(stats),
+          _stream())
+
+
+def ray_loss_invariant_bwd(rgb, rgb_gt, n_rays, depth_pred, depth_gt, mask, n_depth, rgb_l1, w_rgb, w_depth, go,
+                           stats, g_rgb, g_dp, g_dg):
+    """go: four upstream scalars (total, l_rgb, l_depth, l2_mean), each a device tensor or None."""
+    _call("nerf_ray_loss_invariant_bwd", _ptr(rgb), _ptr(rgb_gt), int(n_rays), _ptr(depth_pred), _ptr(depth_gt),
+          _ptr(mask), int(n_depth), int(rgb_l1), float(w_rgb), float(w_depth), *[_ptr(g) for g in go], _ptr(stats),
           _ptr(g_rgb), _ptr(g_dp), _ptr(g_dg), _stream())
 
 

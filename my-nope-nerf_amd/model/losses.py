@@ -16,7 +16,7 @@ from torch.nn import functional as F
 
 from . import _hip
 from .common import inv
-from .rays import ray_loss
+from .rays import can_fuse_invariant, ray_loss, ray_loss_invariant
 
 
 class Loss_Eval(nn.Module):
@@ -192,12 +192,16 @@ class Loss(nn.Module):
         w = weights
         fused = None
         use_depth = w["depth_weight"] != 0.0
+        invariant = use_depth and self.depth_loss_type != "l1"
         if (rgb_pred is not None and rgb_pred.is_cuda and (w["rgb_weight"] != 0.0 or use_depth)
-                and (not use_depth or self.depth_loss_type == "l1")):
+                and (not invariant or (can_fuse_invariant(depth_pred) and depth_gt.numel() == depth_pred.numel()
+                                       and (depth_mask is None or depth_mask.numel() == depth_pred.numel())))):
             # one launch for l_rgb, l_depth, l2_mean and their weighted sum; one for the backward
-            fused = ray_loss(rgb_pred, rgb_gt, depth_pred if use_depth else None,
-                             depth_gt if use_depth else None, depth_mask if use_depth else None,
-                             rgb_loss_type == "l1", w["rgb_weight"], w["depth_weight"])
+            # (the invariant term's medians included: no boolean indexing, no host sync)
+            fn = ray_loss_invariant if invariant else ray_loss
+            fused = fn(rgb_pred, rgb_gt, depth_pred if use_depth else None,
+                       depth_gt if use_depth else None, depth_mask if use_depth else None,
+                       rgb_loss_type == "l1", w["rgb_weight"], w["depth_weight"])
             l_rgb = fused[1] if w["rgb_weight"] != 0.0 else zero
             l_depth = fused[2] if use_depth else zero
         else:

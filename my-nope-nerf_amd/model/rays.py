@@ -286,7 +286,11 @@ class _StepHead(torch.autograd.Function):
             height=a["height"], shift_first=int(bool(a["shift_first"])), flags=a["flags"], lo=float("-inf"),
             c2w=c2w, world=world, M=M, inverses=invs, idx=idx, pixels=pix, rgb=rgb, depth_g=depth_g,
             depth_d=depth_d, cam=cam, ray=ray, view=view, ray_norm=ray_norm, d_src=d_src, mask=mask)
-        _hip.step_head(args, a["descs"])
+        if a.get("valid") is not None or a.get("attempts") is not None:
+            # the draw repeats on the device until a drawn pixel has a valid depth (nerf_step_head_valid)
+            _hip.step_head_valid(args, a.get("valid"), a.get("attempts"), a["descs"])
+        else:
+            _hip.step_head(args, a["descs"])
         depth = depth_d if affine else depth_g
         ctx.save_for_backward(rc, ic, world, M, invs, pix, depth, depth_g, sc, tc2)
         ctx.meta = (R, a["flags"], int(bool(a["shift_first"])), affine, K.shape, scale_mat.shape,
@@ -354,7 +358,9 @@ def step_head(pose, c2w_in, K, scale_mat, aff, a):
     """One launch for the head of a training step.  pose = (r, t, init_c2w) or None with c2w_in
     [4,4]; aff = (scale, shift) or None; a: the non-tensor arguments and the tensors without a
     gradient (img [3,H,W], depth_map [H*W] or None, n_pix, n_rays, width, height, seed,
-    seed_counter, shift_first, flags, descs).  Returns (c2w [4,4], world [1,4,4], ray_idx [R],
+    seed_counter, shift_first, flags, descs, and optionally valid -- a device uint8 / bool [H*W]
+    mask: the draw repeats until a drawn pixel is valid -- and attempts, a device int32 [1] that
+    records the attempt accepted).  Returns (c2w [4,4], world [1,4,4], ray_idx [R],
     pixels [1,R,2], rgb_gt [1,R,3], cam, ray, view, ray_norm, d_src, mask)."""
     r, t, init = pose if pose is not None else (None, None, None)
     sc, sh = aff if aff is not None else (None, None)
@@ -407,12 +413,68 @@ def ray_loss(rgb, rgb_gt, depth_pred, depth_gt, depth_mask, rgb_l1: bool, w_rgb:
                           float(w_depth))
 
 
+class _RayLossInvariant(torch.autograd.Function):
+    """_RayLoss with depth_loss_type 'invariant' (losses.py:35-58): one launch each way, no
+    boolean indexing and no host sync; the medians are kept in `stats` for the backward."""
+
+    @staticmethod
+    def forward(ctx, rgb, rgb_gt, dpred, dgt, mask, l1, w_rgb, w_depth):
+        ctx.set_materialize_grads(False)
+        dev = rgb.device
+        R = rgb.numel() // 3
+        out = [torch.empty((), device=dev, dtype=torch.float32) for _ in range(4)]
+        stats = torch.empty(8, device=dev, dtype=torch.float32)
+        rc, gc, dpc, dgc = _f32c(rgb), _f32c(rgb_gt), _f32c(dpred), _f32c(dgt)
+        mc = None if mask is None else mask.contiguous()
+        n_d = dpc.numel()
+        _hip.ray_loss_invariant(rc, gc, R, dpc, dgc, mc, n_d, l1, w_rgb, w_depth, out, stats)
+        ctx.save_for_backward(rc, gc, dpc, dgc, mc, stats)
+        ctx.meta = (R, n_d, l1, w_rgb, w_depth, rgb.shape, dpred.shape, dgt.shape)
+        return out[0], out[1], out[2], out[3]
+
+    @staticmethod
+    def backward(ctx, g_total, g_rgb_l, g_depth_l, g_l2):
+        rc, gc, dpc, dgc, mc, stats = ctx.saved_tensors
+        R, n_d, l1, w_rgb, w_depth, rshape, pshape, gshape = ctx.meta
+        c = lambda g: None if g is None else g.float().contiguous()
+        want_rgb, want_dp, want_dg = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if not (want_rgb or want_dp or want_dg):
+            return (None,) * 8
+        g_rgb = torch.empty(R, 3, device=rc.device, dtype=torch.float32) if want_rgb else None
+        g_dp = torch.empty(n_d, device=rc.device, dtype=torch.float32) if want_dp else None
+        g_dg = torch.empty(n_d, device=rc.device, dtype=torch.float32) if want_dg else None
+        _hip.ray_loss_invariant_bwd(rc, gc, R, dpc, dgc, mc, n_d, l1, w_rgb, w_depth,
+                                    [c(g_total), c(g_rgb_l), c(g_depth_l), c(g_l2)], stats, g_rgb, g_dp, g_dg)
+        return (g_rgb.reshape(rshape) if want_rgb else None, None,
+                g_dp.reshape(pshape) if want_dp else None, g_dg.reshape(gshape) if want_dg else None,
+                None, None, None, None)
+
+
+def can_fuse_invariant(depth_pred) -> bool:
+    """Whether the invariant depth term fits the fused launch (one workgroup holds the depths)."""
+    return depth_pred is not None and 0 < depth_pred.numel() <= _hip.SAMPLE_MAX_RAYS
+
+
+def ray_loss_invariant(rgb, rgb_gt, depth_pred, depth_gt, depth_mask, rgb_l1: bool, w_rgb: float, w_depth: float):
+    """ray_loss with the median / mean-absolute-deviation normalised depth term of
+    depth_loss_type 'invariant'; depth_pred and depth_gt are dense [n_depth] (n_depth <= 4096),
+    depth_mask bool [n_depth] or None."""
+    if depth_mask is not None and depth_mask.dtype not in (torch.bool, torch.uint8):
+        depth_mask = depth_mask != 0
+    return _RayLossInvariant.apply(rgb, rgb_gt, depth_pred, depth_gt, depth_mask, int(bool(rgb_l1)), float(w_rgb),
+                                   float(w_depth))
+
+
 # ------------------------------------------------------------------ ray sampling
-def sample_rays(n_pix, n_rays, width, height, img=None, seed=None, device=None, seed_counter=None):
+def sample_rays(n_pix, n_rays, width, height, img=None, seed=None, device=None, seed_counter=None, valid=None,
+                attempts=None):
     """Device replacement of ``randperm(n_pix)[:n_rays]`` + the pixel / colour gathers:
     returns (ray_idx int64 [R], pixels [1,R,2], rgb_gt [1,R,3] or None).  ``seed``
     defaults to a draw from torch's host generator (deterministic under manual_seed);
-    ``seed_counter`` (device int64 [1]) makes the draw advance on the device instead."""
+    ``seed_counter`` (device int64 [1]) makes the draw advance on the device instead.
+    ``valid`` (device uint8 / bool [n_pix]) repeats the draw inside the launch until a drawn
+    pixel is valid (training.py:280-283 without the host); ``attempts`` (device int32 [1])
+    records the 1-based attempt accepted."""
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     dev = device if device is not None else img.device
@@ -423,7 +485,11 @@ def sample_rays(n_pix, n_rays, width, height, img=None, seed=None, device=None, 
     if img is not None:
         imc = _f32c(img)
         rgb = torch.empty(1, n_rays, 3, device=dev, dtype=torch.float32)
-    _hip.sample_rays(n_pix, n_rays, seed, width, height, imc, idx, pix, rgb, seed_counter=seed_counter)
+    if valid is None and attempts is None:
+        _hip.sample_rays(n_pix, n_rays, seed, width, height, imc, idx, pix, rgb, seed_counter=seed_counter)
+    else:
+        _hip.sample_rays_valid(n_pix, n_rays, seed, width, height, imc, valid, idx, pix, rgb, attempts=attempts,
+                               seed_counter=seed_counter)
     return idx, pix, rgb
 
 

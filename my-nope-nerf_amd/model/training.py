@@ -6,8 +6,9 @@ runs and what it waits for:
   * the render + its backward are the fused nerf_hip path (rendering.Renderer);
   * the step is free of device->host syncs: the depth-loss mask stays a dense weight,
     the distortion clamp is a ``torch.where``, the "any valid depth among the sampled
-    rays" resampling loop (training.py:280-283) only runs when the image's valid-pixel
-    count (known on the host from the data dict) does not already guarantee it;
+    rays" resampling loop (training.py:280-283) runs inside the sampler's launch, and only
+    when the image's valid-pixel count (known on the host from the data dict, unknown for
+    a device mask) does not already guarantee a valid ray;
   * with torch.distributed initialised (one process per GPU, RCCL), every rank renders
     its own rays and the NeRF / pose / distortion gradients are averaged by ONE
     all-reduce over a flat bucket before the optimiser steps.
@@ -77,6 +78,10 @@ class Trainer(object):
         self._submodules = {}      # module -> its submodule list, for the per-step train-mode check
         self._comm_timer = None    # time_collectives: the all-reduces' (start, end) hipEvents / CPU seconds
         self._seed_one = None      # the backward's persistent d loss / d loss seed (train_step)
+        # the last step's draw attempts (device int32 [1], written by the sampler when it draws against
+        # a depth mask: 1-based, 0 = no valid pixel in 64 attempts); the step never reads it
+        self.draw_attempts = None
+        self._mask_cache = {}      # host depth mask -> (the tensor, its device copy or None): _valid_mask
 
     def time_collectives(self, on=True):
         """Time every gradient all-reduce from now on (hipEvents on the launch stream around
@@ -103,6 +108,52 @@ class Trainer(object):
         sampler keys on a device counter it advances itself (stratified noise comes from
         torch.rand, whose Philox offsets graph replays already advance)."""
         self.seed_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def _valid_mask(self, depth_mask, need_valid, n_pix):
+        """The device mask the sampler has to draw against, or None when an all-invalid draw is
+        ruled out on the host.  A mask is risky when it lives on the device (its valid count is not
+        known here) or when its share of invalid pixels makes an all-invalid draw plausible:
+        (n_invalid / n_pix) ** R > 1e-9.  A risky host mask is uploaded; in graph-capture mode that
+        pageable copy cannot be captured, so the mask has to be on the device already."""
+        if not need_valid or depth_mask is None:
+            return None
+        if not depth_mask.is_cuda:
+            # per host mask tensor (the data dict hands the same one in for every step of an image):
+            # its valid count and, where it is risky, its uploaded copy -- no count and no host-to-device
+            # copy per step.  Keyed on the tensor and its version counter; a few entries at the most.
+            key = (id(depth_mask), depth_mask._version)
+            hit = self._mask_cache.get(key)
+            if hit is not None and hit[0] is depth_mask:
+                if hit[1] is None or self.seed_counter is None:
+                    return hit[1]
+            n_invalid = n_pix - int(depth_mask.sum())
+            if not (n_invalid > 0 and (n_invalid / n_pix) ** self.n_training_points > 1e-9):
+                self._remember_mask(key, depth_mask, None)
+                return None
+            if self.seed_counter is not None:
+                raise RuntimeError(
+                    "Trainer: graph-capture mode (enable_graph_rng) needs this depth mask on the device: its "
+                    "valid-pixel count does not rule out an all-invalid draw (training.py:280-283 resampling), "
+                    "the device sampler redraws against the mask, and a host mask's upload cannot be captured")
+            host, depth_mask = depth_mask, depth_mask.to(self.device)
+        else:
+            host = None
+        m = depth_mask.reshape(-1)
+        if m.dtype not in (torch.bool, torch.uint8):
+            m = m != 0
+        if m.numel() != n_pix:
+            raise ValueError(f"Trainer: depth mask of {m.numel()} pixels for an image of {n_pix}")
+        if self.draw_attempts is None:
+            self.draw_attempts = torch.zeros(1, dtype=torch.int32, device=self.device)
+        m = m.contiguous()
+        if host is not None:
+            self._remember_mask(key, host, m)
+        return m
+
+    def _remember_mask(self, key, host, dev_mask, keep=8):
+        if len(self._mask_cache) >= keep:
+            self._mask_cache.pop(next(iter(self._mask_cache)))
+        self._mask_cache[key] = (host, dev_mask)
 
     # ------------------------------------------------------------------ step
     def _modules_and_optims(self):
@@ -290,15 +341,19 @@ class Trainer(object):
 
         On the device one HIP launch draws the subset and gathers both (rays.sample_rays;
         ``randperm`` sorts n_pix keys to keep R of them).  The validity check is a
-        device->host sync per step in the reference; here it runs only when an all-invalid
-        draw is plausible: with n_invalid of n_pix pixels invalid that probability is
-        <= (n_invalid / n_pix) ** R, computed on the host from the data dict's CPU mask
-        (5 % holes at 1024 rays: 1e-1332)."""
+        device->host sync per step in the reference; here it never is one: when an
+        all-invalid draw is plausible (_valid_mask: a device mask, or a host mask with
+        (n_invalid / n_pix) ** R > 1e-9; 5 % holes at 1024 rays give 1e-1332) the launch itself
+        redraws against the mask until a drawn pixel is valid and records the attempts in
+        ``draw_attempts``.  The host loop remains on the CPU path."""
         dev = self.device
         R = self.n_training_points
         h, w = hw
         B = img.shape[0]
         on_dev = img.is_cuda and B == 1 and can_sample_on_device(n_pix, R)
+
+        valid = self._valid_mask(depth_mask, need_valid, n_pix) if on_dev else None
+        att = self.draw_attempts if valid is not None else None
 
         def draw():
             if on_dev:
@@ -306,28 +361,35 @@ class Trainer(object):
                     # graph-capture mode: a fixed per-rank key and a device step counter, so a
                     # replayed step draws new rays without a host-side seed
                     seed = (0x2545F4914F6CDD1D + self.rank * 0x632BE59BD9B4E019) & 0xFFFFFFFFFFFFFFFF
-                    return sample_rays_dev(n_pix, R, w, h, img[0], seed=seed, seed_counter=self.seed_counter)
+                    return sample_rays_dev(n_pix, R, w, h, img[0], seed=seed, seed_counter=self.seed_counter,
+                                           valid=valid, attempts=att)
                 # host-generator seed (reproducible under torch.manual_seed), decorrelated per
                 # rank so data-parallel ranks render different rays
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item()) + self.rank * 0x632BE59BD9B4E019
-                return sample_rays_dev(n_pix, R, w, h, img[0], seed=seed & 0xFFFFFFFFFFFFFFFF)
+                return sample_rays_dev(n_pix, R, w, h, img[0], seed=seed & 0xFFFFFFFFFFFFFFFF, valid=valid,
+                                       attempts=att)
             ray_idx = torch.randperm(n_pix, device=dev)[:R]
             rgb_gt = img.view(B, 3, n_pix).permute(0, 2, 1)[:, ray_idx]
             return ray_idx, self._pixels(h, w, dev)[:, ray_idx], rgb_gt
 
         ray_idx, p, rgb_gt = draw()
-        if need_valid and depth_mask is not None:
+        if not on_dev and need_valid and depth_mask is not None:
+            # the reference's host loop, only where the device sampler does not draw: a CPU image,
+            # a batch of images, or fewer than 2 R pixels
             if depth_mask.is_cuda:
                 risky = True
             else:
                 n_invalid = n_pix - int(depth_mask.sum())
                 risky = n_invalid > 0 and (n_invalid / n_pix) ** R > 1e-9
             if risky and self.seed_counter is not None:
-                # graph-capture mode: the resample-until-valid loop needs the host to look at
-                # the draw (a sync inside capture) and a replay could never re-decide it
+                # graph-capture mode: the host loop would have to look at the draw (a sync inside
+                # capture) and a replay could never re-decide it; _valid_mask's message covers the
+                # device sampler's path
                 raise RuntimeError(
-                    "Trainer: graph-capture mode (enable_graph_rng) needs a depth mask on the host whose "
-                    "valid-pixel count rules out an all-invalid draw (training.py:280-283 resampling)")
+                    "Trainer: graph-capture mode (enable_graph_rng) cannot run the host resampling loop "
+                    "(training.py:280-283) this step needs: the device sampler does not draw here (one GPU image "
+                    "with at least 2 * n_training_points pixels is required) and the depth mask's valid-pixel "
+                    "count does not rule out an all-invalid draw")
             if risky:
                 m = depth_mask.flatten().to(dev)
                 while not m[ray_idx].any():
@@ -338,8 +400,9 @@ class Trainer(object):
     def _step_head_applies(self, img, depth_input, depth_mask, need_valid):
         """Whether this step's head runs as the single nerf_step_head launch: NERF_STEP_HEAD not 0,
         one image on the GPU that the device sampler can draw from, no injected draw, an H x W
-        depth prior that is data, a LearnPose (or no) pose net with a fixed init_c2w, and an
-        all-invalid draw ruled out on the host (graph mode's rule)."""
+        depth prior that is data, and a LearnPose (or no) pose net with a fixed init_c2w.  A depth
+        mask that does not rule out an all-invalid draw no longer keeps the step off it: the launch
+        redraws against the mask (_valid_mask, nerf_step_head_valid)."""
         if not step_head_enabled() or self.inject is not None or self.rendering_technique != "nope_nerf":
             return False
         B, _, h, w = img.shape
@@ -355,16 +418,11 @@ class Trainer(object):
         rcfg = getattr(getattr(self.model, "renderer", None), "cfg", None)
         if rcfg is None or "normalise_ray" not in rcfg or "use_ray_dir" not in rcfg:
             return False
-        if need_valid and depth_mask is not None:
-            if depth_mask.is_cuda:
-                return False
-            n_pix = h * w
-            n_invalid = n_pix - int(depth_mask.sum())
-            if n_invalid > 0 and (n_invalid / n_pix) ** self.n_training_points > 1e-9:
-                return False
+        if need_valid and depth_mask is not None and depth_mask.numel() != h * w:
+            return False
         return True
 
-    def _step_head(self, img, depth_input, img_idx, pose_gt, camera_mat, scale_mat, aff):
+    def _step_head(self, img, depth_input, img_idx, pose_gt, camera_mat, scale_mat, aff, valid=None):
         """The head of the step in one launch (rays.step_head): returns (c2w, world_mat [1,4,4],
         ray_idx, pixels, rgb_gt, rays) with rays = (cam, ray, view, ray_norm, d_src, mask) for
         Renderer.nope_nerf; the field runner's weights are packed by the same launch and marked so."""
@@ -386,7 +444,8 @@ class Trainer(object):
         descs = runner.pack_descs() if runner is not None else ()
         a = {"img": img[0], "depth_map": depth_input.reshape(-1), "n_pix": h * w, "n_rays": self.n_training_points,
              "width": w, "height": h, "seed": seed, "seed_counter": self.seed_counter,
-             "shift_first": self.shift_first, "flags": flags, "descs": descs}
+             "shift_first": self.shift_first, "flags": flags, "descs": descs, "valid": valid,
+             "attempts": self.draw_attempts if valid is not None else None}
         c2w, world_mat, ray_idx, p, rgb_gt, *rays = step_head(pose, c2w_in, camera_mat, scale_mat, aff, a)
         if runner is not None:
             runner.prepacked = True
@@ -459,8 +518,9 @@ class Trainer(object):
             extra["noise"] = noise.to(dev)
         elif head:
             aff = (scale_input, shift_input) if affine_in is not None else None
+            valid = self._valid_mask(depth_mask, data.get("img.dpt") is None, h * w)
             c2w, world_mat, ray_idx, p, rgb_gt, extra["rays"] = self._step_head(
-                img, depth_input, img_idx, pose_gt, camera_mat, scale_mat, aff)
+                img, depth_input, img_idx, pose_gt, camera_mat, scale_mat, aff, valid)
         else:
             ray_idx, p, rgb_gt = self.sample_rays(h * w, depth_mask, data.get("img.dpt") is None, img=img,
                                                   hw=(h, w))
