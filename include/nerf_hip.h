@@ -673,6 +673,24 @@ int nerf_camera_rays_bwd(const float* M, const float* pixels, const float* depth
                          const float* g_cam, const float* g_ray, const float* g_view, const float* g_norm,
                          const float* g_dsrc, float* gM, float* g_depth, void* stream);
 
+/* The NDC warp of the LLFF configs (sample_option 'ndc'; an addition within ABI 15), replacing
+ * common.py:632-675 as called from rendering.py:169-181 and rendering.py:158-159:
+ * o_ndc, d_ndc [R][3] of cam, ray [R][3]; fx = K[0], fy = K[5] read on the device (K is the
+ * [4][4] camera matrix, so a learned focal needs no host value); near as in the reference
+ * call (1.0).  d_src / d_gt optional: d_gt [R] = 1 - 1 / d_src (rendering.py:158-159).
+ * One thread per ray, the reference's f32 operation order. */
+int nerf_ndc_rays(const float* cam, const float* ray, const float* K, float near, int n_rays,
+                  const float* d_src, float* o_ndc, float* d_ndc, float* d_gt, void* stream);
+/* upstream g_o, g_d, g_dgt (each optional) -> g_cam, g_ray [R][3], gK [4][4] (only [0][0] and
+ * [1][1] non-zero, the rest written as zero; optional), g_dsrc [R] (optional).  Deterministic.
+ * The closed form (the shifted origin's z is -near, so the third components pass no gradient),
+ * evaluated in f64 and rounded once; with gK one workgroup walks all rays and sums the two
+ * focal terms in a fixed order, without it the rays spread over the grid.  g_dsrc = g_dgt /
+ * d_src^2, and 0 where g_dgt is 0 (a masked ray with d_src = 0 passes 0 on, not 0 / 0). */
+int nerf_ndc_rays_bwd(const float* cam, const float* ray, const float* K, float near, int n_rays,
+                      const float* d_src, const float* g_o, const float* g_d, const float* g_dgt,
+                      float* g_cam, float* g_ray, float* gK, float* g_dsrc, void* stream);
+
 /* The head of a training step in ONE launch (additive entry, ABI version unchanged): the ray
  * set-up before the per-sample work (training.py:277-288, rendering.py:52-98, common.py:13-40,
  * :139-141, :205-208 and :277-310, poses.py:23-31, network.py:24-26) and the weight pack of

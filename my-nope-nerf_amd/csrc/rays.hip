@@ -9,6 +9,8 @@
 //                       inv(scale) @ inv(world) @ inv(K) (common.py:139-141, 205-208);
 //   * k_camera_rays   : origin, unit direction, |P1 - o|, d_src and the depth mask per ray
 //                       (rendering.py:52-80) and its backward (pose / distortion learning);
+//   * k_ndc_rays(_bwd): the NDC warp of those rays for sample_option 'ndc' (common.py:632-675,
+//                       rendering.py:169-181) with d_gt = 1 - 1 / d_src (rendering.py:158-159);
 //   * k_ray_loss(_bwd): rgb l1/l2 + masked depth l1 + l2_mean and their gradients
 //                       (losses.py:28-33, 60-66, 164-228);
 //   * k_sample_rays_valid: the draw repeated until a drawn pixel has a valid depth
@@ -435,6 +437,106 @@ __global__ __launch_bounds__(1024) void k_camera_rays_bwd(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------
+// NDC warp of the LLFF configs (common.py:632-675 called from rendering.py:169-181 with near = 1,
+// and rendering.py:158-159's d_gt = 1 - 1 / d_src), one thread per ray:
+//   t = -(near + o_z) / d_z;  p = o + t d (the origin shifted to the near plane, p_z = -near);
+//   ox = p_x / p_z, oy = p_y / p_z, o2 = 1 + 2 near / p_z;  a = -1 / (1 / fx), b = -1 / (1 / fy);
+//   o_ndc = (a ox, b oy, o2);  d_ndc = (a (d_x / d_z - ox), b (d_y / d_z - oy), 1 - o2)
+// in the reference's operation order, f32, contraction off.  fx = K[0], fy = K[5] are read here.
+constexpr int NDC_THREADS = 256;
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(NDC_THREADS) void k_ndc_rays(const float* __restrict__ cam, const float* __restrict__ ray,
+                                                          const float* __restrict__ K, float near, int R,
+                                                          const float* __restrict__ d_src, float* __restrict__ o_ndc,
+                                                          float* __restrict__ d_ndc, float* __restrict__ d_gt) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const float fx = K[0], fy = K[5];
+    const float o0 = cam[3 * r], o1 = cam[3 * r + 1], o2 = cam[3 * r + 2];
+    const float d0 = ray[3 * r], d1 = ray[3 * r + 1], d2 = ray[3 * r + 2];
+    const float t = -(near + o2) / d2;
+    const float p0 = o0 + t * d0, p1 = o1 + t * d1, p2 = o2 + t * d2;
+    const float ox = p0 / p2, oy = p1 / p2;
+    const float z = 1.0f + (2.0f * near) / p2;
+    const float a = -1.0f / (1.0f / fx), b = -1.0f / (1.0f / fy);
+    o_ndc[3 * r] = a * ox;
+    o_ndc[3 * r + 1] = b * oy;
+    o_ndc[3 * r + 2] = z;
+    d_ndc[3 * r] = a * (d0 / d2 - ox);
+    d_ndc[3 * r + 1] = b * (d1 / d2 - oy);
+    d_ndc[3 * r + 2] = 1.0f - z;
+    if (d_gt != nullptr) d_gt[r] = 1.0f - 1.0f / d_src[r];
+}
+
+// Its backward, in closed form rather than along the chain of the expressions: the shifted
+// origin's z is -near whatever the ray, so o2 and 1 - o2 are constants (their upstream gradients
+// reach nothing) and 1 / p_z = -1 / near; a = -fx, b = -fy.  With r0 = d_x / d_z, r1 = d_y / d_z:
+//   g_ox = a (gO_x - gD_x), g_p0 = -g_ox / near (same in y);  g_t = g_p0 d_x + g_p1 d_y
+//   g_cam = (g_p0, g_p1, -g_t / d_z)
+//   g_ray = (g_p0 t + a gD_x / d_z, g_p1 t + b gD_y / d_z, -(g_t t + a gD_x r0 + b gD_y r1) / d_z)
+//   g_fx = -sum gO_x ox + gD_x (r0 - ox), g_fy likewise;  g_dsrc = g_dgt / d_src^2
+// evaluated in f64 from the f32 inputs and rounded once.  Without gK every block takes its own
+// rays; with gK the launch is one workgroup that walks all rays, and the two focal sums are f64
+// per-thread sums over a fixed ray stride, a wave butterfly, then the wave sums in order
+// (deterministic, no atomics).
+constexpr int NDC_BWD_THREADS = 1024;
+
+__global__ __launch_bounds__(NDC_BWD_THREADS) void k_ndc_rays_bwd(
+    const float* __restrict__ cam, const float* __restrict__ ray, const float* __restrict__ K, float near, int R,
+    const float* __restrict__ d_src, const float* __restrict__ g_o, const float* __restrict__ g_d,
+    const float* __restrict__ g_dgt, float* __restrict__ g_cam, float* __restrict__ g_ray, float* __restrict__ gK,
+    float* __restrict__ g_dsrc) {
+    __shared__ double red[NDC_BWD_THREADS / 64][2];
+    const double a = -(double)K[0], b = -(double)K[5], ip2 = -1.0 / (double)near;
+    double sfx = 0.0, sfy = 0.0;
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < R; r += gridDim.x * blockDim.x) {
+        const double o0 = cam[3 * r], o1 = cam[3 * r + 1], o2 = cam[3 * r + 2];
+        const double d0 = ray[3 * r], d1 = ray[3 * r + 1], d2 = ray[3 * r + 2];
+        const double t = -((double)near + o2) / d2;
+        const double ox = (o0 + t * d0) * ip2, oy = (o1 + t * d1) * ip2;
+        const double r0 = d0 / d2, r1 = d1 / d2;
+        const double gO0 = g_o ? (double)g_o[3 * r] : 0.0, gO1 = g_o ? (double)g_o[3 * r + 1] : 0.0;
+        const double gD0 = g_d ? (double)g_d[3 * r] : 0.0, gD1 = g_d ? (double)g_d[3 * r + 1] : 0.0;
+        const double g_r0 = a * gD0, g_r1 = b * gD1;
+        const double g_p0 = a * (gO0 - gD0) * ip2, g_p1 = b * (gO1 - gD1) * ip2;
+        const double g_t = g_p0 * d0 + g_p1 * d1;
+        g_cam[3 * r] = (float)g_p0;
+        g_cam[3 * r + 1] = (float)g_p1;
+        g_cam[3 * r + 2] = (float)(-g_t / d2);
+        g_ray[3 * r] = (float)(g_p0 * t + g_r0 / d2);
+        g_ray[3 * r + 1] = (float)(g_p1 * t + g_r1 / d2);
+        g_ray[3 * r + 2] = (float)(-(g_t * t + g_r0 * r0 + g_r1 * r1) / d2);
+        sfx -= gO0 * ox + gD0 * (r0 - ox);
+        sfy -= gO1 * oy + gD1 * (r1 - oy);
+        if (g_dsrc != nullptr) {
+            // a ray whose d_gt took no gradient passes none on: 0, not 0 / 0, at d_src = 0 (the
+            // rays without a depth prior, which the dense depth loss masks out)
+            const double ds = d_src[r], g = g_dgt ? (double)g_dgt[r] : 0.0;
+            g_dsrc[r] = g != 0.0 ? (float)(g / (ds * ds)) : 0.f;
+        }
+    }
+    if (gK == nullptr) return;      // the same for every thread of the launch
+    sfx = wave_sum_d(sfx);
+    sfy = wave_sum_d(sfy);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) { red[wv][0] = sfx; red[wv][1] = sfy; }
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        double s = 0.0;
+        if (threadIdx.x == 0 || threadIdx.x == 5)
+            for (int w = 0; w < NDC_BWD_THREADS / 64; ++w) s += red[w][threadIdx.x == 0 ? 0 : 1];
+        gK[threadIdx.x] = (float)s;
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // losses.py:28-33 (rgb l1/l2 over R rays), :60-66 (depth l1 over the masked rays), l2_mean
 // = mse(rgb, gt), total = w_rgb l_rgb + w_depth l_depth.  out = {total, l_rgb, l_depth,
 // l2_mean} (four scalars), cnt = number of depth rays used (for the backward).
@@ -522,11 +624,6 @@ __device__ __forceinline__ uint32_t float_key(float x) {     // a < b  <=>  key(
 }
 __device__ __forceinline__ float key_float(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 // the sums of v[0..N) over the workgroup, the same bits in every thread; red: [LI_WAVES][N]
 template <int N>
@@ -869,6 +966,29 @@ extern "C" int nerf_camera_rays_bwd(const float* M, const float* pixels, const f
     NERF_CHECK(g_depth == nullptr || depth != nullptr, "%s: g_depth without depth", __func__);
     hipLaunchKernelGGL(k_camera_rays_bwd, dim3(1), dim3(1024), 0, as_stream(stream), M, pixels, depth, n_rays,
                        flags, g_cam, g_ray, g_view, g_norm, g_dsrc, gM, g_depth);
+    return check_launch(__func__);
+}
+
+extern "C" int nerf_ndc_rays(const float* cam, const float* ray, const float* K, float near, int n_rays,
+                             const float* d_src, float* o_ndc, float* d_ndc, float* d_gt, void* stream) {
+    NERF_CHECK_PTR(cam); NERF_CHECK_PTR(ray); NERF_CHECK_PTR(K); NERF_CHECK_PTR(o_ndc); NERF_CHECK_PTR(d_ndc);
+    NERF_CHECK(n_rays > 0, "%s: n_rays=%d", __func__, n_rays);
+    NERF_CHECK(d_gt == nullptr || d_src != nullptr, "%s: d_gt without d_src", __func__);
+    hipLaunchKernelGGL(k_ndc_rays, dim3((n_rays + NDC_THREADS - 1) / NDC_THREADS), dim3(NDC_THREADS), 0,
+                       as_stream(stream), cam, ray, K, near, n_rays, d_src, o_ndc, d_ndc, d_gt);
+    return check_launch(__func__);
+}
+
+extern "C" int nerf_ndc_rays_bwd(const float* cam, const float* ray, const float* K, float near, int n_rays,
+                                 const float* d_src, const float* g_o, const float* g_d, const float* g_dgt,
+                                 float* g_cam, float* g_ray, float* gK, float* g_dsrc, void* stream) {
+    NERF_CHECK_PTR(cam); NERF_CHECK_PTR(ray); NERF_CHECK_PTR(K); NERF_CHECK_PTR(g_cam); NERF_CHECK_PTR(g_ray);
+    NERF_CHECK(n_rays > 0, "%s: n_rays=%d", __func__, n_rays);
+    NERF_CHECK(g_dsrc == nullptr || d_src != nullptr, "%s: g_dsrc without d_src", __func__);
+    // the focal sums need every ray in one workgroup; without them the rays spread over the grid
+    const int blocks = gK != nullptr ? 1 : (n_rays + NDC_BWD_THREADS - 1) / NDC_BWD_THREADS;
+    hipLaunchKernelGGL(k_ndc_rays_bwd, dim3(blocks), dim3(NDC_BWD_THREADS), 0, as_stream(stream), cam, ray, K, near,
+                       n_rays, d_src, g_o, g_d, g_dgt, g_cam, g_ray, gK, g_dsrc);
     return check_launch(__func__);
 }
 

@@ -178,6 +178,8 @@ _SIGS = {
     "nerf_depth_affine_bwd": ([_c_p, _c_i, _c_p, _c_p, _c_i, _c_f, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_camera_rays": ([_c_p, _c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_camera_rays_bwd": ([_c_p, _c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_ndc_rays": ([_c_p, _c_p, _c_p, _c_f, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_ndc_rays_bwd": ([_c_p, _c_p, _c_p, _c_f, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_step_head": ([ctypes.POINTER(StepHeadRays), ctypes.POINTER(PackDesc), _c_i, _c_p], _c_i),
     "nerf_step_head_valid": ([ctypes.POINTER(StepHeadRays), _c_p, _c_p, ctypes.POINTER(PackDesc), _c_i, _c_p], _c_i),
     "nerf_ray_loss_invariant": ([_c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_i, _c_i, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p,
@@ -593,6 +595,20 @@ def camera_rays(M, pixels, depth, n_rays, flags, cam, ray, view, ray_norm, d_src
 def camera_rays_bwd(M, pixels, depth, n_rays, flags, g_cam, g_ray, g_view, g_norm, g_dsrc, gM, g_depth):
     _call("nerf_camera_rays_bwd", _ptr(M), _ptr(pixels), _ptr(depth), int(n_rays), int(flags), _ptr(g_cam),
           _ptr(g_ray), _ptr(g_view), _ptr(g_norm), _ptr(g_dsrc), _ptr(gM), _ptr(g_depth), _stream())
+
+
+def ndc_rays(cam, ray, K, near, n_rays, d_src, o_ndc, d_ndc, d_gt=None):
+    """The NDC warp of cam, ray [R][3] with fx = K[0], fy = K[5] of the [4][4] camera matrix K;
+    d_gt [R] = 1 - 1 / d_src when both are given."""
+    _call("nerf_ndc_rays", _ptr(cam), _ptr(ray), _ptr(K), float(near), int(n_rays), _ptr(d_src), _ptr(o_ndc),
+          _ptr(d_ndc), _ptr(d_gt), _stream())
+
+
+def ndc_rays_bwd(cam, ray, K, near, n_rays, d_src, g_o, g_d, g_dgt, g_cam, g_ray, gK=None, g_dsrc=None):
+    """g_o, g_d [R][3] and g_dgt [R] (each a device tensor or None) -> g_cam, g_ray [R][3], gK [4][4]
+    and g_dsrc [R] (the last two optional)."""
+    _call("nerf_ndc_rays_bwd", _ptr(cam), _ptr(ray), _ptr(K), float(near), int(n_rays), _ptr(d_src), _ptr(g_o),
+          _ptr(g_d), _ptr(g_dgt), _ptr(g_cam), _ptr(g_ray), _ptr(gK), _ptr(g_dsrc), _stream())
 
 
 def step_head(rays: Optional[StepHeadRays], descs: Sequence[PackDesc] = ()):

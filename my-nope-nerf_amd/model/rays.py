@@ -4,8 +4,8 @@
 The reference builds every step's rays from ~150 ATen launches: ``randperm`` + gathers
 (training.py:277-283), ``Exp``/``make_c2w`` (common.py:277-310), three 4x4 inversions per
 unprojection (common.py:139-141, 205-208), ``transform_to_world``/``origin_to_world``
-(rendering.py:52-80) and the loss terms with their autograd backward (losses.py:28-66,
-164-228).  Here each is one launch, wrapped in an autograd Function whose backward is
+(rendering.py:52-80), the NDC warp of the LLFF configs (common.py:632-675) and the loss terms
+with their autograd backward (losses.py:28-66, 164-228).  Here each is one launch, wrapped in an autograd Function whose backward is
 exact (the camera-ray and loss backwards are HIP kernels; the 4x4 chains, which only
 need gradients when poses / focals are learned, use the closed-form matrix identities).
 
@@ -250,6 +250,54 @@ def camera_rays_hip(M, pixels, depth, normalise_ray=True, view_ones=False):
     """(cam, ray, view, ray_norm, d_src, mask) of pixels [1,R,2], depth [1,R,1] or None."""
     flags = (_hip.RAYS_NORMALISE if normalise_ray else 0) | (_hip.RAYS_VIEW_ONES if view_ones else 0)
     return _CameraRays.apply(M, pixels, depth, flags)
+
+
+# ------------------------------------------------------------------ NDC warp
+class _NdcRays(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cam, ray, camera_mat, near, d_src):
+        ctx.set_materialize_grads(False)      # o_ndc / d_ndc / d_gt each often get no gradient
+        cc, rc, Kc = _f32c(cam).reshape(-1, 3), _f32c(ray).reshape(-1, 3), _f32c(camera_mat)
+        dc = None if d_src is None else _f32c(d_src).reshape(-1)
+        R = cc.shape[0]
+        o_ndc, d_ndc = torch.empty_like(cc), torch.empty_like(cc)
+        d_gt = None if dc is None else torch.empty_like(dc)
+        _hip.ndc_rays(cc, rc, Kc, near, R, dc, o_ndc, d_ndc, d_gt)
+        ctx.save_for_backward(cc, rc, Kc, dc)
+        ctx.meta = (near, R, cam.shape, ray.shape, camera_mat.shape, None if d_src is None else d_src.shape)
+        if d_gt is None:
+            return o_ndc.view(cam.shape), d_ndc.view(ray.shape), None
+        return o_ndc.view(cam.shape), d_ndc.view(ray.shape), d_gt.view(d_src.shape)
+
+    @staticmethod
+    def backward(ctx, g_o, g_d, g_dgt):
+        cc, rc, Kc, dc = ctx.saved_tensors
+        near, R, csh, rsh, Ksh, dsh = ctx.meta
+        want_c, want_r, want_K = ctx.needs_input_grad[:3]
+        want_ds = dc is not None and ctx.needs_input_grad[4]
+        if not (want_c or want_r or want_K or want_ds) or (g_o is None and g_d is None and g_dgt is None):
+            return None, None, None, None, None
+        c = lambda g: None if g is None else g.float().contiguous()
+        g_cam, g_ray = torch.empty_like(cc), torch.empty_like(rc)
+        gK = torch.empty(4, 4, device=cc.device, dtype=torch.float32) if want_K else None
+        g_ds = torch.empty_like(dc) if want_ds else None
+        _hip.ndc_rays_bwd(cc, rc, Kc, near, R, dc, c(g_o), c(g_d), c(g_dgt), g_cam, g_ray, gK, g_ds)
+        return (g_cam.view(csh) if want_c else None, g_ray.view(rsh) if want_r else None,
+                gK.view(Ksh) if want_K else None, None, g_ds.view(dsh) if want_ds else None)
+
+
+def ndc_rays(cam, ray, camera_mat, near=1.0, d_src=None):
+    """get_ndc_rays_fxfy (common.py:632-675) of cam, ray [R,3] with fx, fy = camera_mat[0,0,0],
+    camera_mat[0,1,1] read on the device, and d_gt = 1 - 1 / d_src (rendering.py:158-159) from the
+    same launch: (o_ndc, d_ndc, d_gt or None).  One launch forward and one backward; the gradient of
+    camera_mat has the matrix's own shape.  Device tensors only."""
+    if camera_mat.numel() != 16:
+        raise ValueError("ndc_rays: one camera per call (batch 1)")
+    if cam.shape != ray.shape or cam.shape[-1] != 3:
+        raise ValueError(f"ndc_rays: cam and ray must both be [R, 3], got {tuple(cam.shape)} and {tuple(ray.shape)}")
+    if d_src is not None and d_src.numel() != cam.numel() // 3:
+        raise ValueError("ndc_rays: d_src must hold one value per ray")
+    return _NdcRays.apply(cam, ray, camera_mat, float(near), d_src)
 
 
 # ------------------------------------------------------------------ the step head

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from .common import get_mask, get_ndc_rays_fxfy, unproject_matrix
-from .rays import camera_rays_hip
+from .rays import camera_rays_hip, ndc_rays
 from .field import F_DIST_ALPHA, F_RELU, F_WHITE_BKGD, render_field, render_field_eval
 
 epsilon = 1e-6  # rendering.py:9 (applied inside the composite kernel)
@@ -220,7 +220,14 @@ class Renderer(nn.Module):
                                                           cfg["normalise_ray"])
             view = -ray if cfg["use_ray_dir"] else torch.ones_like(ray)
         R = cam.shape[0]
-        if cfg["sample_option"] == "ndc":        # rendering.py:169-181 (no jitter)
+        ndc = cfg["sample_option"] == "ndc"
+        ndc_hip = ndc and cam.is_cuda
+        if ndc_hip:                              # rendering.py:169-181 and :158-159 in one launch
+            if eval_ and cfg["normalise_ray"]:   # rendering.py:144-148 comes before the 1 - 1 / d
+                d_src = d_src / ray_norm
+            pts_o, pts_d, d_src = ndc_rays(cam, ray, camera_mat, 1.0, d_src)
+            near_s, far_s, nz = 0.0, 1.0, None
+        elif ndc:                                # rendering.py:169-181 (no jitter)
             fxfy = torch.cat([camera_mat[:, 0, 0], camera_mat[:, 1, 1]])
             pts_o, pts_d = get_ndc_rays_fxfy(fxfy, 1.0, cam, ray)
             near_s, far_s, nz = 0.0, 1.0, None
@@ -240,8 +247,9 @@ class Renderer(nn.Module):
                 if nz is None else render_field(self.model, pts_o, pts_d, view, nz, near_s, far_s, S, flags)
         if eval_ and cfg["normalise_ray"]:       # rendering.py:144-148
             dist = dist / ray_norm
-            d_src = d_src / ray_norm
-        if cfg["sample_option"] == "ndc":
+            if not ndc_hip:
+                d_src = d_src / ray_norm
+        if ndc and not ndc_hip:
             d_src = 1 - 1 / d_src
         normal = None
         if not eval_ and cfg.get("normal_loss", False):          # rendering.py:127-137
