@@ -691,6 +691,65 @@ int nerf_ndc_rays_bwd(const float* cam, const float* ray, const float* K, float 
                       const float* d_src, const float* g_o, const float* g_d, const float* g_dgt,
                       float* g_cam, float* g_ray, float* gK, float* g_dsrc, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * The per-ray logic of the geometry visualisation (march.hip; rendering_technique
+ * 'phong_renderer', rendering.py:199-468; additions within ABI 15).  Four plain per-ray kernels
+ * around the field launches above (model/geometry.py::phong_frame): every call is dense over all
+ * n_rays rays, so a whole frame needs no boolean index, no host sync and no data-dependent shape.
+ * state [R] (u8) of a ray: 1 = bracket found, 2 = first sample already occupied (distance 0),
+ * 0 = no surface (distance inf). */
+#define NERF_MARCH_NONE 0
+#define NERF_MARCH_BRACKET 1
+#define NERF_MARCH_INSIDE 2
+/* rendering.py:447-468 (get_sphere_intersection, far root) and the d_proposal set-up of
+ * rendering.py:262-300.  cam, ray [R][3]; the sphere |x| = rad is intersected from c = cam[0] for
+ * every ray, as the reference passes ray0[:, 0]:
+ *   b = ray . c,  u = b^2 - (|c|^2 - rad^2),  d_far [R] = u > 0 ? max(sqrt(u) - b, 0) : 0,
+ * evaluated in f64 from the f32 inputs and rounded once.  The n_steps samples of a ray,
+ * d(j) = d0 (1 - t_j) + d_far t_j with t = linspace(0, 1, n_steps), are handed to the render
+ * kernels as G = n_steps / seg pseudo-rays (seg >= 2 divides n_steps), ray-major:
+ *   o_seg [R][G][3] = cam + ray (d0 + (d_far - d0) g seg / (n_steps - 1)),
+ *   d_seg [R][G][3] = ray (d_far - d0) (seg - 1) / (n_steps - 1),
+ * each formed in f64 from the rounded d_far and rounded once: pseudo-ray (r, g) rendered with
+ * near = 0, far = 1 and seg samples gives samples g seg .. g seg + seg - 1 of ray r, so an
+ * alpha [R G][seg] output is the [R][n_steps] occupancy array as it lies in memory. */
+int nerf_march_rays(const float* cam, const float* ray, int n_rays, float rad, float d0, int n_steps, int seg,
+                    float* d_far, float* o_seg, float* d_seg, void* stream);
+/* rendering.py:300-360: the first sign change of val = occ - tau (f32) along each ray.
+ * occ [R][n], n >= 2.  j* = the smallest j < n - 1 with val[j] val[j+1] < 0, the product formed
+ * in f32 (a zero, an underflow to -0 or a NaN is no change, as torch.sign gives 0 for each; a
+ * negative subnormal is one).  state = 2 when
+ * !(val[0] < 0); else 1 when j* exists and val[j*] < 0; else 0 -- a later change after a first
+ * one that goes positive to negative is not looked for, as in the reference.  For state 1:
+ * f_low = val[j*], f_high = val[j*+1], d_low = d(j*), d_high = d(j*+1) with d(j) as above, formed in
+ * f64 and rounded once (as nerf_march_rays places the samples); zeros for the other states.  One wave per ray, lanes striding
+ * over j, the first change by ballot. */
+int nerf_march_select(const float* occ, int n_rays, int n, const float* d_far, float d0, float tau,
+                      uint8_t* state, float* f_low, float* f_high, float* d_low, float* d_high, void* stream);
+/* rendering.py:405-436, one secant update for every ray.  first != 0: d_pred =
+ * -f_low (d_high - d_low) / (f_high - f_low) + d_low from the bracket (raw4 unused).  Otherwise
+ * f_mid = act(raw4[r][0]) - tau, raw4 [R][4] the field's raw head outputs at the previous p_mid
+ * and act the model's density activation (softplus, or ReLU with NERF flag 4; then
+ * 1 - exp(-sigma) unless flag 1, dist_alpha); the bracket is updated by the reference's four
+ * `where`s (f_mid < 0 moves the low end, anything else the high end) and d_pred formed anew;
+ * a ray whose previous d_pred was not finite keeps it.  f_low, f_high, d_low, d_high, d_pred [R]
+ * are read and written in place (d_pred only written when first).  Outputs:
+ *   p_mid [R][3] = cam + d_pred ray (separate multiply and add), the next field input;
+ *   d_i [R] = d_pred for state 1, 0 for state 2, inf for state 0.
+ * For a ray whose state is not 1 or whose d_pred is not finite, p_mid is its camera position:
+ * no non-finite point reaches the field kernels. */
+int nerf_secant_step(int first, const float* raw4, int flags, float tau, const uint8_t* state, const float* cam,
+                     const float* ray, int n_rays, float* f_low, float* f_high, float* d_low, float* d_high,
+                     float* d_pred, float* p_mid, float* d_i, void* stream);
+/* rendering.py:236-271: headlight Phong shading.  g [R][3] = -d sigma_raw / dp and raw4 [R][4] at
+ * the surface points; light = cam[0] / |cam[0]|, normal = g / |g| (no epsilon, as the reference).
+ * On the rays with state 1 and a finite d_i:
+ *   rgb [R][3] = min(0.3 + 0.7 max(normal . light, 0), 1) in all three channels,
+ *   rgb_surf [R][3] = sigmoid(raw4[r][1:4]);
+ * elsewhere rgb = 1 (background) and rgb_surf = 0. */
+int nerf_phong_shade(const float* g, const float* raw4, const uint8_t* state, const float* d_i, const float* cam,
+                     int n_rays, float* rgb, float* rgb_surf, void* stream);
+
 /* The head of a training step in ONE launch (additive entry, ABI version unchanged): the ray
  * set-up before the per-sample work (training.py:277-288, rendering.py:52-98, common.py:13-40,
  * :139-141, :205-208 and :277-310, poses.py:23-31, network.py:24-26) and the weight pack of

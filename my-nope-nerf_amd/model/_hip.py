@@ -180,6 +180,11 @@ _SIGS = {
     "nerf_camera_rays_bwd": ([_c_p, _c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_ndc_rays": ([_c_p, _c_p, _c_p, _c_f, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_ndc_rays_bwd": ([_c_p, _c_p, _c_p, _c_f, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_march_rays": ([_c_p, _c_p, _c_i, _c_f, _c_f, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_march_select": ([_c_p, _c_i, _c_i, _c_p, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_secant_step": ([_c_i, _c_p, _c_i, _c_f, _c_p, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+                          _c_p], _c_i),
+    "nerf_phong_shade": ([_c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p], _c_i),
     "nerf_step_head": ([ctypes.POINTER(StepHeadRays), ctypes.POINTER(PackDesc), _c_i, _c_p], _c_i),
     "nerf_step_head_valid": ([ctypes.POINTER(StepHeadRays), _c_p, _c_p, ctypes.POINTER(PackDesc), _c_i, _c_p], _c_i),
     "nerf_ray_loss_invariant": ([_c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_i, _c_i, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p,
@@ -609,6 +614,77 @@ def ndc_rays_bwd(cam, ray, K, near, n_rays, d_src, g_o, g_d, g_dgt, g_cam, g_ray
     and g_dsrc [R] (the last two optional)."""
     _call("nerf_ndc_rays_bwd", _ptr(cam), _ptr(ray), _ptr(K), float(near), int(n_rays), _ptr(d_src), _ptr(g_o),
           _ptr(g_d), _ptr(g_dgt), _ptr(g_cam), _ptr(g_ray), _ptr(gK), _ptr(g_dsrc), _stream())
+
+
+MARCH_NONE, MARCH_BRACKET, MARCH_INSIDE = 0, 1, 2   # NERF_MARCH_*
+
+
+def _march_check(name, f32=(), u8=()):
+    for t in f32:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise RuntimeError(f"{name}: float32 contiguous tensors expected")
+    for t in u8:
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise RuntimeError(f"{name}: uint8 contiguous state expected")
+
+
+def march_rays(cam, ray, rad, d0, n_steps, seg):
+    """cam, ray [R][3] -> (d_far [R], o_seg [R*G][3], d_seg [R*G][3]), G = n_steps / seg pseudo-rays
+    per ray in ray-major order (nerf_march_rays)."""
+    _march_check("march_rays", (cam, ray))
+    R = cam.shape[0]
+    if cam.shape != (R, 3) or ray.shape != (R, 3):
+        raise ValueError(f"march_rays: cam / ray must be [R][3], got {tuple(cam.shape)} and {tuple(ray.shape)}")
+    if seg < 2 or n_steps % seg:
+        raise ValueError(f"march_rays: seg={seg} must be >= 2 and divide n_steps={n_steps}")
+    G = n_steps // seg
+    d_far = torch.empty(R, device=cam.device)
+    o_seg, d_seg = torch.empty(R * G, 3, device=cam.device), torch.empty(R * G, 3, device=cam.device)
+    _call("nerf_march_rays", _ptr(cam), _ptr(ray), R, float(rad), float(d0), int(n_steps), int(seg), _ptr(d_far),
+          _ptr(o_seg), _ptr(d_seg), _stream())
+    return d_far, o_seg, d_seg
+
+
+def march_select(occ, d_far, d0, tau):
+    """occ [R][n], d_far [R] -> (state [R] uint8, f_low, f_high, d_low, d_high [R]) (nerf_march_select)."""
+    _march_check("march_select", (occ, d_far))
+    if occ.dim() != 2 or occ.shape[1] < 2 or d_far.numel() != occ.shape[0]:
+        raise ValueError(f"march_select: occ [R][n >= 2] and d_far [R] expected, got {tuple(occ.shape)}, "
+                         f"{tuple(d_far.shape)}")
+    R, n = occ.shape
+    state = torch.empty(R, device=occ.device, dtype=torch.uint8)
+    out = [torch.empty(R, device=occ.device) for _ in range(4)]
+    _call("nerf_march_select", _ptr(occ), R, n, _ptr(d_far), float(d0), float(tau), _ptr(state),
+          *[_ptr(t) for t in out], _stream())
+    return (state, *out)
+
+
+def secant_step(first, raw4, flags, tau, state, cam, ray, bracket, d_pred, p_mid, d_i):
+    """One secant update of every ray (nerf_secant_step); bracket = (f_low, f_high, d_low, d_high), updated in
+    place with d_pred [R]; p_mid [R][3] and d_i [R] are written.  raw4: [>= R][4] at the previous p_mid
+    (None when first)."""
+    R = state.numel()
+    _march_check("secant_step", (raw4, cam, ray, *bracket, d_pred, p_mid, d_i), (state,))
+    if raw4 is not None and (raw4.dim() != 2 or raw4.shape[1] != 4 or raw4.shape[0] < R):
+        raise ValueError(f"secant_step: raw4 must be [>= {R}][4], got {tuple(raw4.shape)}")
+    if any(t.numel() != R for t in (*bracket, d_pred, d_i)) or any(t.numel() != 3 * R for t in (cam, ray, p_mid)):
+        raise ValueError("secant_step: per-ray tensors of the wrong size")
+    _call("nerf_secant_step", int(bool(first)), _ptr(raw4), int(flags), float(tau), _ptr(state), _ptr(cam), _ptr(ray),
+          R, *[_ptr(t) for t in bracket], _ptr(d_pred), _ptr(p_mid), _ptr(d_i), _stream())
+
+
+def phong_shade(g, raw4, state, d_i, cam):
+    """g [R][3] = -d sigma_raw / dp, raw4 [>= R][4] at the surface points -> (rgb [R][3], rgb_surf [R][3])
+    (nerf_phong_shade)."""
+    R = state.numel()
+    _march_check("phong_shade", (g, raw4, d_i, cam), (state,))
+    if raw4.dim() != 2 or raw4.shape[1] != 4 or raw4.shape[0] < R or g.numel() != 3 * R or d_i.numel() != R \
+            or cam.numel() != 3 * R:
+        raise ValueError("phong_shade: per-ray tensors of the wrong size")
+    rgb, rgb_surf = torch.empty(R, 3, device=g.device), torch.empty(R, 3, device=g.device)
+    _call("nerf_phong_shade", _ptr(g), _ptr(raw4), _ptr(state), _ptr(d_i), _ptr(cam), R, _ptr(rgb), _ptr(rgb_surf),
+          _stream())
+    return rgb, rgb_surf
 
 
 def step_head(rays: Optional[StepHeadRays], descs: Sequence[PackDesc] = ()):

@@ -88,12 +88,16 @@ class Extract_Images(object):
 
         geo_out = None
         if output_geo:
-            # Phong-shaded occupancy surface (rendering.py:199-258) in 1024-pixel chunks
+            # Phong-shaded occupancy surface (rendering.py:199-258): the whole frame in one call on the
+            # GPU (Renderer.phong_frame), the reference's 1024-pixel chunks for CPU tensors
             pixels = arange_pixels(resolution=(h, w), device=self.device)[1]
             with torch.no_grad():
-                geo = torch.cat([self.renderer(p, None, camera_mat, world_mat, scale_mat, "phong_renderer", eval_=True,
-                                               it=it, add_noise=False)["rgb"] for p in torch.split(pixels, 1024, dim=1)],
-                                dim=1)
+                if pixels.is_cuda:
+                    geo = self.renderer.phong_frame(pixels, camera_mat, world_mat, scale_mat, it)["rgb"]
+                else:
+                    geo = torch.cat([self.renderer(p, None, camera_mat, world_mat, scale_mat, "phong_renderer",
+                                                   eval_=True, it=it, add_noise=False)["rgb"]
+                                     for p in torch.split(pixels, 1024, dim=1)], dim=1)
             geo_out = (geo.view(h, w, 3).cpu().numpy() * 255).astype(np.uint8)
             geo_dir = os.path.join(render_dir, "geo_out")
             os.makedirs(geo_dir, exist_ok=True)

@@ -117,6 +117,14 @@ class Renderer(nn.Module):
         self.model.train(was_training)
         return {"rgb": rgb.reshape(B, -1, 3), "normal": None, "rgb_surf": rgb_surf.reshape(B, -1, 3)}
 
+    def phong_frame(self, pixels, camera_mat, world_mat, scale_mat, it, n_steps=512, n_secant_steps=8, tau=0.5):
+        """phong_renderer for a whole frame of GPU pixels in one call, without its chunk loop, boolean
+        indices and host syncs (model/geometry.py, csrc/march.hip); the dict also carries 'd_i' [1, R]
+        and 'mask' [R]."""
+        from .geometry import phong_frame
+        return phong_frame(self, pixels, camera_mat, world_mat, scale_mat, it, n_steps=n_steps,
+                           n_secant_steps=n_secant_steps, tau=tau)
+
     def ray_marching(self, ray0, ray_direction, model, c=None, tau=0.5, n_steps=[128, 129], n_secant_steps=8,
                      depth_range=[0.0, 2.4], max_points=3500000, rad=1.0):
         """rendering.py:262-403: evaluate n_steps samples between depth_range[0] and the far
