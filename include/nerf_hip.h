@@ -351,7 +351,11 @@ int nerf_gemm_debug_ablate(int mask);
  * outputs: the f32 activation (the backward's saved tensor; NULL in eval renders), the ReLU
  * bits and the column maxima per 128-row group (mode 2's weight-gradient scales; not for
  * the colour layer).  enc_p / enc_d and their row maxima as written by nerf_encode_samples.
- * n_pad % 128 == 0. */
+ * n_pad % 128 == 0.
+ * nerf_mlp_chain_fwd is the plain ten-linear kernel (one wave per SIMD, no heads, no
+ * encodings, no composite) and nothing else: the eval fallback when a ray's samples do not
+ * tile the 128-row block.  Training and the per-ray eval render run the two-wave kernels of
+ * the entries below. */
 typedef struct {
     const uint16_t* img;   /* fp16 pair image of the packed weight */
     int img_rows;          /* its rows (>= the layer's outputs) */
@@ -445,8 +449,10 @@ int nerf_mlp_chain_bwd(const nerf_chain_bwd* a, void* stream);
  * unused.  An addition within ABI 15. */
 int nerf_mlp_chain_bwd_rays(const nerf_chain_bwd* a, void* stream);
 
-/* Diagnostics only: per-block phase cycles of nerf_mlp_chain_fwd into buf[(n_pad/128)*6]
- * uint64 (DMA wait, barrier, MFMA section, epilogue, total, end time); NULL switches off. */
+/* Diagnostics only: per-block phase cycles of the chain kernels into buf[(n_pad/128)*6] uint64;
+ * NULL switches off.  nerf_mlp_chain_fwd's kernel always stamps (DMA wait, barrier, MFMA
+ * section, epilogue, total, end time); the two-wave kernels only in a NERF_CHAIN_STAMPS
+ * build (DMA wait, barrier, prologue, epilogues, total, tail). */
 int nerf_chain_debug_stamps(void* buf);
 /* 1 when the library was built with NERF_CHAIN_STAMPS (the two-wave chains then stamp too;
  * production builds carry no stamp instructions in them), else 0. */

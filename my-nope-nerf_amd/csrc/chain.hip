@@ -1,7 +1,19 @@
-// Fused forward chain of the field MLP (GEMM precision mode 2, hidden width 256).
+// Fused chains of the field MLP (GEMM precision mode 2, hidden width 256): six kernels.
+//   k_mlp_chain_fwd        the ten linears, one wave per SIMD (nerf_mlp_chain_fwd): the eval
+//                          fallback when a ray's samples do not tile the 128-row block -- no
+//                          encodings, no heads, no composite
+//   k_render_fused2        the per-ray eval render (nerf_render_eval_fused)          } namespace f2,
+//   k_mlp_chain_train2     the training forward (nerf_mlp_chain_train)               } two waves
+//   k_mlp_chain_frozen     ... without its saves (nerf_mlp_chain_frozen)             } per SIMD
+//   k_mlp_chain_bwd        the input-gradient chain (nerf_mlp_chain_bwd)             } namespace b2,
+//   k_mlp_chain_bwd_rays   ... storing only the ray gradients' operands (_bwd_rays)  } on f2's pieces
+// The two-wave kernels share one schedule calculator (wait_n and its kin) and one copy of the
+// device pieces (f2::dma_ring, dma_n, split_pair, cm_at, frag_read, tiles), each under a chain
+// description (f2::Chain, b2::Chain); the host entries share the descriptor and backward checks
+// (chain_layers_checked, chain_bwd_checked).
 //
-// OfficialStaticNerf's ten linears (official_nerf.py:20-37, 60-91) run in ONE launch: a
-// block owns 128 sample rows (4 waves x 32 rows) and walks them through
+// The one-wave kernel: OfficialStaticNerf's ten linears (official_nerf.py:20-37, 60-91) run in
+// ONE launch: a block owns 128 sample rows (4 waves x 32 rows) and walks them through
 //   l0 [enc_p] -> l1 -> l2 -> l3 -> l4 [h3, enc_p] -> l5 -> l6 -> l7 -> lf -> lr [f, enc_d]
 // with the activation tile resident in registers between layers.  Per layer a wave holds
 //   * its A operand: 32 rows x K as row-scaled fp16 pairs (x 2^e = hi + lo, the split of
@@ -104,9 +116,9 @@ struct ChainFwdArgs {
     int n_pad;
     nerf_chain_layer L[CNL];
     unsigned long long* stamps;   // diagnostics (nerf_chain_debug_stamps): per-block phase cycles or NULL
-    // the fused per-ray eval render (nerf_render_eval_fused): samples + encodings in the
-    // prologue, density / colour heads in the l7 / colour-layer epilogues, sigma -> alpha ->
-    // composite of the block's rays at the end
+    // the two-wave kernels only.  The fused per-ray eval render (nerf_render_eval_fused): samples
+    // + encodings in the prologue, density / colour heads in the l7 / colour-layer epilogues,
+    // sigma -> alpha -> composite of the block's rays at the end
     const float* po; const float* pd; const float* view;   // [R][3]
     int R, S, flags;
     float near_z, far_z;
@@ -124,7 +136,6 @@ struct ChainState {
     char* ring; char* leb16; float* lbias; uint32_t* lcm;   // leb16: [2][256 rows][16 B], exponent in word 0
     char* lenc; float* lrp; float* lrd;                      // encoding tile [128][64], row maxima [128] x 2
     float* stage;                                            // this wave's [32][STG_LD] epilogue tile
-    float* fx;                                               // fused eval: wd [256], wc [3][128], raw [128][4], z [128]
     int tid, lane, sl, hf;
     size_t m0, row;
     int er;                          // row exponent of the current A operand
@@ -152,16 +163,13 @@ constexpr int ENC_D_STEP = 4 + 16 * 3 + 20;   // kbase(5): the enc_d tile replac
 // LDS-DMA instructions every wave issues with global k-step tt (uniform across waves):
 // 4 for the weight ring, +2 at a layer's first step (weight-row exponents, biases), +10 at
 // step 0 (enc_p tile 8, enc_p / enc_d row maxima 1 + 1), +8 at ENC_D_STEP (enc_d tile)
-// (fused eval: the encodings are computed in-kernel, so step 0 and ENC_D_STEP carry no extras)
-constexpr int dma_count(int tt, bool fused = false) {
-    return tt >= CT ? 0
-                    : DMA_PER_STEP + (first_step(tt) ? 2 : 0) + (tt == 0 && !fused ? 10 : 0) +
-                          (tt == ENC_D_STEP && !fused ? 8 : 0);
+constexpr int dma_count(int tt) {
+    return tt >= CT ? 0 : DMA_PER_STEP + (first_step(tt) ? 2 : 0) + (tt == 0 ? 10 : 0) + (tt == ENC_D_STEP ? 8 : 0);
 }
 // DMAs issued after those of step tt by the time step tt is consumed (steps tt+1 .. tt+NSLOT-2)
-constexpr int dma_after(int tt, bool fused = false) {
+constexpr int dma_after(int tt) {
     int n = 0;
-    for (int u = tt + 1; u <= tt + NSLOT - 2; ++u) n += dma_count(u, fused);
+    for (int u = tt + 1; u <= tt + NSLOT - 2; ++u) n += dma_count(u);
     return n;
 }
 
@@ -177,7 +185,7 @@ __device__ __forceinline__ void chain_dma_enc(const float* enc, ChainState& st) 
 }
 
 // global k-step TT -> ring slot TT % NSLOT, plus the extras of dma_count(TT)
-template <int TT, bool F>
+template <int TT>
 __device__ __forceinline__ void chain_dma(const ChainFwdArgs& p, ChainState& st) {
     if constexpr (TT < CT) {
         constexpr int l = [] { int i = 0; while (kbase(i + 1) <= TT) ++i; return i; }();
@@ -204,29 +212,29 @@ __device__ __forceinline__ void chain_dma(const ChainFwdArgs& p, ChainState& st)
             if (st.lane < 16)
                 cdma16(L.bias, (uint32_t)((64 * wr + 4 * st.lane) * 4), reinterpret_cast<char*>(st.lbias + (l & 1) * 256 + 64 * wr));
         }
-        if constexpr (TT == 0 && !F) {
+        if constexpr (TT == 0) {
             chain_dma_enc(p.enc_p, st);
             if (st.lane < 8) {   // 32 row maxima per wave
                 cdma16(p.rp + st.m0, (uint32_t)((32 * w + 4 * st.lane) * 4), reinterpret_cast<char*>(st.lrp + 32 * w));
                 cdma16(p.rd + st.m0, (uint32_t)((32 * w + 4 * st.lane) * 4), reinterpret_cast<char*>(st.lrd + 32 * w));
             }
         }
-        if constexpr (TT == ENC_D_STEP && !F) chain_dma_enc(p.enc_d, st);
+        if constexpr (TT == ENC_D_STEP) chain_dma_enc(p.enc_d, st);
     }
 }
 
 // one k-step of layer l: wait for its slot, publish, refill the ring, MFMAs
-template <int l, int s, bool F>
+template <int l, int s>
 __device__ __forceinline__ void chain_kstep(const ChainFwdArgs& p, ChainState& st) {
     constexpr int TT = kbase(l) + s;
     constexpr int nreg = l == 0 ? 0 : 16;
     constexpr int ntj = L_OUT[l] / 32;
     chain_tick(p, st, st.t_mma);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(dma_after(TT, F)) : "memory");   // this step's DMAs landed
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(dma_after(TT)) : "memory");   // this step's DMAs landed
     chain_tick(p, st, st.t_wait);
     __syncthreads();
     chain_tick(p, st, st.t_bar);
-    chain_dma<TT + NSLOT - 1, F>(p, st);
+    chain_dma<TT + NSLOT - 1>(p, st);
     if constexpr (s == 0) {
         // layer prologue (behind a barrier): the previous layer's column maxima out, this
         // layer's column-max accumulators zeroed (its exponents and biases arrived by DMA)
@@ -259,7 +267,7 @@ __device__ __forceinline__ void chain_kstep(const ChainFwdArgs& p, ChainState& s
         st.acc[j] = cmfma(bh[j % 3], al, st.acc[j]);   // hi . lo
         st.acc[j] = cmfma(bl[j % 3], ah, st.acc[j]);   // lo . hi
         st.acc[j] = cmfma(bh[j % 3], ah, st.acc[j]);   // hi . hi
-        if constexpr (l > 0 && s < nreg && !F) {
+        if constexpr (l > 0 && s < nreg) {
             if (j == 1 && p.L[l - 1].out) {
                 // the previous layer's output, stored beside this layer's MFMAs instead of in a
                 // burst at its epilogue: this k-step's 8 features of the row, rebuilt from the
@@ -282,11 +290,11 @@ __device__ __forceinline__ void chain_kstep(const ChainFwdArgs& p, ChainState& s
     }
 }
 
-template <int l, int s, bool F>
+template <int l, int s>
 __device__ __forceinline__ void chain_ksteps(const ChainFwdArgs& p, ChainState& st) {
     if constexpr (s < L_KS[l]) {
-        chain_kstep<l, s, F>(p, st);
-        chain_ksteps<l, s + 1, F>(p, st);
+        chain_kstep<l, s>(p, st);
+        chain_ksteps<l, s + 1>(p, st);
     }
 }
 
@@ -299,105 +307,8 @@ __device__ __forceinline__ void enc_frags(ChainState& st, int rl) {
         frag_from8(src[4 * s + 2 * st.hf], src[4 * s + 2 * st.hf + 1], st.er, st.enc_hi[s], st.enc_lo[s]);
 }
 
-// fused eval: the view-direction encodings of the block's rays (27 values of
-// encode_position L = 4, official_nerf.py:87, 99-119, zero padded to 32) and their maxima
-// live in LDS, one 36-float record per ray (fx + FX_ENCD): the view direction is per ray,
-// so 128 / S records serve the block's 128 rows
-constexpr int FX_RAW = 640, FX_Z = 1152, FX_ENCD = 1280, ENCD_REC = 36;
-__device__ __forceinline__ void fused_encode_d(const ChainFwdArgs& p, float* fx, int tid, size_t m0) {
-    const int nr = CROWS / p.S;
-    if (tid >= nr) return;
-    const size_t ray = m0 / (size_t)p.S + tid;
-    float d[3] = {0.f, 0.f, 0.f};
-    if (ray < (size_t)p.R) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) d[c] = p.view[3 * ray + c];
-    }
-    float* rec = fx + FX_ENCD + ENCD_REC * tid;
-    float m = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { rec[c] = d[c]; m = fmaxf(m, fabsf(d[c])); }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float f = (float)(1 << i);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float sn, cs;
-            sincosf(f * d[c], &sn, &cs);
-            rec[3 + 6 * i + c] = sn;
-            rec[6 + 6 * i + c] = cs;
-            m = fmaxf(m, fmaxf(fabsf(sn), fabsf(cs)));
-        }
-    }
-#pragma unroll
-    for (int c = 27; c < 32; ++c) rec[c] = 0.f;
-    rec[32] = m;
-}
-// the same records spread over threads t0 .. t0 + nt - 1 (nt a multiple of 64): sixteen lanes
-// (one DPP row) per ray, lane i < 12 one (level i / 3, coordinate i % 3) sin / cos pair, lane 12
-// the direction itself, the record's max by a row reduction -- the same values as
-// fused_encode_d, 12 sincosf deep on one thread there, one here
-// the direction of the ray whose record lane u of the range works on in pass rb (zero past the
-// rays): loaded before the prologue's LDS-DMAs for pass 0
-__device__ __forceinline__ void encd_load(const ChainFwdArgs& p, int u, int nt, size_t m0, int rb, float (&d)[3]) {
-    const int nr = CROWS / p.S;
-    const int r = rb + (u >> 4);
-    const size_t ray = m0 / (size_t)p.S + r;
-    const bool live = u >= 0 && u < nt && r < nr && ray < (size_t)p.R;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) d[c] = live ? p.view[3 * ray + c] : 0.f;
-}
-__device__ __forceinline__ void fused_encode_d_rows(const ChainFwdArgs& p, float* fx, int tid, int t0, int nt,
-                                                    size_t m0, const float (&d0)[3]) {
-    const int nr = CROWS / p.S;
-    const int u = tid - t0;
-    if (u < 0 || u >= nt) return;
-    const int i = u & 15;
-    for (int rb = 0; rb < nr; rb += nt / 16) {   // block-uniform trip count: the row shuffles stay converged
-        const int r = rb + (u >> 4);
-        float dv[3] = {d0[0], d0[1], d0[2]};
-        if (rb > 0) encd_load(p, u, nt, m0, rb, dv);
-        float m = 0.f;
-        if (r < nr) {
-            float* rec = fx + FX_ENCD + ENCD_REC * r;
-            if (i < 12) {
-                const int lv = i / 3, c = i % 3;
-                const float d = c == 0 ? dv[0] : c == 1 ? dv[1] : dv[2];
-                float sn, cs;
-                sincosf((float)(1 << lv) * d, &sn, &cs);
-                rec[3 + 6 * lv + c] = sn;
-                rec[6 + 6 * lv + c] = cs;
-                m = fmaxf(fabsf(sn), fabsf(cs));
-            } else if (i == 12) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    rec[c] = dv[c];
-                    m = fmaxf(m, fabsf(dv[c]));
-                }
-            } else if (i == 13) {
-#pragma unroll
-                for (int c = 27; c < 32; ++c) rec[c] = 0.f;
-            }
-        }
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if (r < nr && i == 0) fx[FX_ENCD + ENCD_REC * r + 32] = m;
-    }
-}
-// this lane's 4 encoding k-steps (8-feature chunks 16 s + 8 hf .. + 7; columns >= 32 zero)
-__device__ __forceinline__ void enc_d_frags(ChainState& st, const float* rec) {
-    const float4* src = reinterpret_cast<const float4*>(rec);
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const float4 u = s < 2 ? src[4 * s + 2 * st.hf] : z4;
-        const float4 v = s < 2 ? src[4 * s + 2 * st.hf + 1] : z4;
-        frag_from8(u, v, st.er, st.enc_hi[s], st.enc_lo[s]);
-    }
-}
-
 // layer l: k-loop, epilogue (features f = 32 j + 8 q + 4 hf + c of row st.row), next A
-template <int l, bool F>
+template <int l>
 __device__ __forceinline__ void chain_layer(const ChainFwdArgs& p, ChainState& st) {
     constexpr int ntj = L_OUT[l] / 32;
     constexpr bool relu = l != 8;
@@ -406,14 +317,8 @@ __device__ __forceinline__ void chain_layer(const ChainFwdArgs& p, ChainState& s
     for (int j = 0; j < 8; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) st.acc[j][r] = 0.f;
-    chain_ksteps<l, 0, F>(p, st);
+    chain_ksteps<l, 0>(p, st);
     chain_tick(p, st, st.t_mma);
-    // fused eval heads: sigma_raw = fc_density(h8) in l7's epilogue, the colour logits
-    // fc_rgb(hr) in the colour layer's (official_nerf.py:66, 91), partial dots over this
-    // lane's features, the lane halves summed below
-    constexpr bool head_d = F && l == 7, head_c = F && l == CNL - 1;
-    float hs0 = 0.f, hs1 = 0.f, hs2 = 0.f;
-
     // the colour layer stores its output here; every other layer's output is stored by the
     // next layer's k-steps (chain_kstep)
     const bool store_here = l == CNL - 1 && L.out != nullptr;
@@ -481,55 +386,14 @@ __device__ __forceinline__ void chain_layer(const ChainFwdArgs& p, ChainState& s
             }
         }
     }
-    if constexpr (head_d || head_c) {
-        // the head dots over the epilogue's results (acc now holds the layer output), one
-        // feature quad at a time: the scheduling barriers keep the weight reads from being
-        // hoisted into one 128-register burst
-#pragma unroll
-        for (int j = 0; j < ntj; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                __builtin_amdgcn_sched_barrier(0);
-                const int f0 = 32 * j + 8 * q + 4 * st.hf;
-                const float x0 = st.acc[j][4 * q], x1 = st.acc[j][4 * q + 1];
-                const float x2 = st.acc[j][4 * q + 2], x3 = st.acc[j][4 * q + 3];
-                if constexpr (head_d) {
-                    const float4 wv = *reinterpret_cast<const float4*>(st.fx + f0);
-                    hs0 += x0 * wv.x + x1 * wv.y + x2 * wv.z + x3 * wv.w;
-                } else {
-                    const float4 w0 = *reinterpret_cast<const float4*>(st.fx + 256 + f0);
-                    const float4 w1 = *reinterpret_cast<const float4*>(st.fx + 384 + f0);
-                    const float4 w2 = *reinterpret_cast<const float4*>(st.fx + 512 + f0);
-                    hs0 += x0 * w0.x + x1 * w0.y + x2 * w0.z + x3 * w0.w;
-                    hs1 += x0 * w1.x + x1 * w1.y + x2 * w1.z + x3 * w1.w;
-                    hs2 += x0 * w2.x + x1 * w2.y + x2 * w2.z + x3 * w2.w;
-                }
-            }
-        __builtin_amdgcn_sched_barrier(0);
-        // raw4 row (sigma_raw, rgb logits) of this sample into the block's LDS rows
-        float* raw = st.fx + FX_RAW + 4 * ((st.tid >> 6) * 32 + st.sl);
-        hs0 += __shfl_xor(hs0, 32, 64);
-        if constexpr (head_d) {
-            if (st.hf == 0) raw[0] = hs0 + p.bd[0];
-        } else {
-            hs1 += __shfl_xor(hs1, 32, 64);
-            hs2 += __shfl_xor(hs2, 32, 64);
-            if (st.hf == 0) {
-                raw[1] = hs0 + p.bc[0];
-                raw[2] = hs1 + p.bc[1];
-                raw[3] = hs2 + p.bc[2];
-            }
-        }
-    }
     chain_tick(p, st, st.t_epi);
     if constexpr (l < CNL - 1) {
         // next layer's A operand: row exponent over the row's 256 features (and the encoding
         // joined in the next layer), fp16 pairs, quad exchange between the lane halves
         float m = fmaxf(rmx, __shfl_xor(rmx, 32, 64));
         const int rl = (st.tid >> 6) * 32 + st.sl;   // row inside the block
-        const float* drec = F ? st.fx + FX_ENCD + ENCD_REC * (rl / (F ? p.S : 1)) : nullptr;
-        if constexpr (l == 3) m = fmaxf(m, F ? fmaxf(st.lrp[rl], st.lrd[rl]) : st.lrp[rl]);
-        if constexpr (l == 8) m = fmaxf(m, F ? drec[32] : st.lrd[rl]);
+        if constexpr (l == 3) m = fmaxf(m, st.lrp[rl]);
+        if constexpr (l == 8) m = fmaxf(m, st.lrd[rl]);
         st.er = row_exp(m);
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
@@ -553,156 +417,19 @@ __device__ __forceinline__ void chain_layer(const ChainFwdArgs& p, ChainState& s
             st.act_hi[s] = make_uint4(h0[0], h1[0], h0[1], h1[1]);
             st.act_lo[s] = make_uint4(l0[0], l1[0], l0[1], l1[1]);
         }
-        if constexpr (l == 3 || (l == 8 && !F)) enc_frags(st, rl);   // the enc_p / enc_d tile in LDS
-        if constexpr (l == 8 && F) enc_d_frags(st, drec);
+        if constexpr (l == 3 || l == 8) enc_frags(st, rl);   // the enc_p / enc_d tile in LDS
         chain_tick(p, st, st.t_epi);
     }
 }
 
-// fused eval prologue: samples (rendering.py:183-198, no jitter) and the position encoding
-// (official_nerf.py:61, 99-119) of the block's 128 rows into the LDS tile the chain reads
-// (the layout nerf_encode_samples writes), with row maxima and z.  Waves 0-1 write columns
-// 0..32 (x, levels 0-4), waves 2-3 columns 33..63 (levels 5-9, zero pad): no divergence.
-__device__ __forceinline__ void fused_encode_p(const ChainFwdArgs& p, ChainState& st) {
-    const int row = st.tid & 127, half = st.tid >> 7;
-    const size_t g = st.m0 + row;
-    float* dst = reinterpret_cast<float*>(st.lenc + row * 256);
-    float x[3] = {0.f, 0.f, 0.f}, z = 0.f;
-    const bool live = g < (size_t)p.R * p.S;
-    if (live) {
-        const size_t ray = g / (size_t)p.S;
-        const int i = (int)(g - ray * (size_t)p.S);
-        z = lerp_z(linspace01(i, p.S), p.near_z, p.far_z);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) x[c] = ray_point(p.po[3 * ray + c], p.pd[3 * ray + c], z);
-    }
-    float m = 0.f;
-    if (half == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { dst[c] = x[c]; m = fmaxf(m, fabsf(x[c])); }
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const float f = (float)(1 << i);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float sn, cs;
-                sincosf(f * x[c], &sn, &cs);
-                dst[3 + 6 * i + c] = sn;
-                dst[6 + 6 * i + c] = cs;
-                m = fmaxf(m, fmaxf(fabsf(sn), fabsf(cs)));
-            }
-        }
-        st.fx[FX_Z + row] = z;
-        if (live) p.z[g] = z;
-    } else {
-#pragma unroll
-        for (int i = 5; i < 10; ++i) {
-            const float f = (float)(1 << i);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float sn, cs;
-                sincosf(f * x[c], &sn, &cs);
-                dst[3 + 6 * i + c] = sn;
-                dst[6 + 6 * i + c] = cs;
-                m = fmaxf(m, fmaxf(fabsf(sn), fabsf(cs)));
-            }
-        }
-        dst[63] = 0.f;
-    }
-    // the two halves' maxima of a row: lrp (columns 0..32) and lrd (33..63; lrd holds no
-    // enc_d maxima in the fused kernel); readers take the max of both
-    (half == 0 ? st.lrp : st.lrd)[row] = m;
-}
-
-// fused eval epilogue: sigma -> alpha -> exclusive-product compositing of the block's
-// 128 / S rays (rendering.py:113-141), from the raw4 / z rows in LDS, with the arithmetic of
-// k_composite16_fwd (so the fused and the unfused render agree bit for bit): one 16-lane DPP
-// row per ray, lane l owning samples [l J, l J + J) (J = max(1, S / 16)); transmittance by a
-// row prefix-product scan, the sums by row butterflies; each lane stores its J alphas as
-// contiguous float4s (a ray's S alphas are one contiguous run across its row)
-template <int J, int NTH>
-__device__ __forceinline__ void fused_composite16(const ChainFwdArgs& p, const float* fx, int tid, size_t m0) {
-    const int S = p.S;
-    const int nr = CROWS / S;
-    const int l16 = tid & 15;
-    for (int rb = 0; rb < nr; rb += NTH / 16) {    // NTH / 16 rays per pass of the block
-        const int rloc = rb + (tid >> 4);
-        const size_t ray = m0 / (size_t)S + rloc;
-        const bool active = rloc < nr && ray < (size_t)p.R;   // whole 16-lane rows are (in)active
-        const int i0 = l16 * J;
-        float al[J], T[J], c[J][3], z[J];
-        bool valid[J];
-        float pl = 1.f;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const int i = i0 + j;
-            valid[j] = active && i < S;
-            float a = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, zz = 0.f;
-            if (valid[j]) {
-                const int e = rloc * S + i;
-                const float4 r = *reinterpret_cast<const float4*>(fx + FX_RAW + 4 * e);
-                zz = fx[FX_Z + e];
-                const float sg = f_density(r.x, p.flags);
-                if (p.flags & F_DIST_ALPHA)
-                    a = i == S - 1 ? 1.f : 1.f - __expf(-1.0f * sg * (fx[FX_Z + e + 1] - zz));   // rendering.py:116-122
-                else
-                    a = 1.f - __expf(-1.0f * sg);
-                c0 = f_sigmoid(r.y); c1 = f_sigmoid(r.z); c2 = f_sigmoid(r.w);
-            }
-            al[j] = a; z[j] = zz;
-            c[j][0] = c0; c[j][1] = c1; c[j][2] = c2;
-            T[j] = pl;
-            pl *= valid[j] ? (1.f - a + kEps) : 1.f;
-        }
-        const float excl = dpp_f<0x111>(1.f, row_scan_mul(pl));   // product over the lanes before this one
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, sd = 0.f, sw = 0.f;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const float w = al[j] * (T[j] * excl);
-            s0 += w * c[j][0];
-            s1 += w * c[j][1];
-            s2 += w * c[j][2];
-            sd += w * z[j];
-            sw += w;
-        }
-        float* ao = p.alpha + ray * (size_t)S + i0;
-        if (J % 4 == 0 && active) {
-#pragma unroll
-            for (int q = 0; q < J / 4; ++q)
-                *reinterpret_cast<float4*>(ao + 4 * q) = make_float4(al[4 * q], al[4 * q + 1], al[4 * q + 2], al[4 * q + 3]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < J; ++j)
-                if (valid[j]) ao[j] = al[j];
-        }
-        s0 = row_sum(s0); s1 = row_sum(s1); s2 = row_sum(s2); sd = row_sum(sd);
-        if (p.flags & F_WHITE_BKGD) sw = row_sum(sw);
-        if (active && l16 == 0) {
-            if (p.flags & F_WHITE_BKGD) {          // rendering.py:139-141
-                const float bg = 1.f - sw;
-                s0 += bg; s1 += bg; s2 += bg;
-            }
-            p.rgb[3 * ray + 0] = s0;
-            p.rgb[3 * ray + 1] = s1;
-            p.rgb[3 * ray + 2] = s2;
-            p.dist[ray] = sd;
-        }
-    }
-}
-
-template <int NTH>
-__device__ __forceinline__ void fused_composite(const ChainFwdArgs& p, const float* fx, int tid, size_t m0) {
-    if (p.S >= 128) fused_composite16<8, NTH>(p, fx, tid, m0);
-    else if (p.S >= 64) fused_composite16<4, NTH>(p, fx, tid, m0);
-    else if (p.S >= 32) fused_composite16<2, NTH>(p, fx, tid, m0);
-    else fused_composite16<1, NTH>(p, fx, tid, m0);
-}
-
+// (F is unused and only <false> is instantiated: the parameter keeps the kernel's symbol,
+// k_mlp_chain_fwd<false>, its section and its place in the object as they were -- the device
+// code of this file was held identical across the removal of the fused <true> paths,
+// profiles/chain_refactor/isa_identity.txt)
 template <bool F>
 __global__ __launch_bounds__(256) void k_mlp_chain_fwd(ChainFwdArgs p) {
     constexpr int RING = NSLOT * SBYTES, LEB = 2 * 4096, LBIAS = 2 * 256 * 4, LCM = 2 * 256 * 4, LENC = 128 * 256;
     constexpr int LSTG = 4 * 32 * STG_LD * 4;
-    static_assert(LSTG >= (FX_ENCD + ENCD_REC * 64) * 4, "the fused eval buffers live in the staging region");
     __shared__ __attribute__((aligned(16))) char smem[RING + LEB + LBIAS + LCM + LENC + 2 * 512 + LSTG];
     ChainState st;
     st.ring = smem;
@@ -713,7 +440,6 @@ __global__ __launch_bounds__(256) void k_mlp_chain_fwd(ChainFwdArgs p) {
     st.lrp = reinterpret_cast<float*>(st.lenc + LENC);
     st.lrd = st.lrp + 128;
     st.stage = reinterpret_cast<float*>(st.lenc + LENC + 2 * 512) + (threadIdx.x >> 6) * 32 * STG_LD;
-    st.fx = reinterpret_cast<float*>(st.lenc + LENC + 2 * 512);
     st.tid = threadIdx.x;
     st.lane = st.tid & 63; st.sl = st.lane & 31; st.hf = st.lane >> 5;
     st.m0 = (size_t)blockIdx.x * CROWS;
@@ -722,40 +448,29 @@ __global__ __launch_bounds__(256) void k_mlp_chain_fwd(ChainFwdArgs p) {
     st.t_last = __builtin_amdgcn_s_memtime();
     const unsigned long long t_start = st.t_last;
 
-    chain_dma<0, F>(p, st);
-    chain_dma<1, F>(p, st);
-    chain_dma<2, F>(p, st);
-    chain_dma<3, F>(p, st);
+    chain_dma<0>(p, st);
+    chain_dma<1>(p, st);
+    chain_dma<2>(p, st);
+    chain_dma<3>(p, st);
     static_assert(NSLOT == 5, "prologue issues NSLOT - 1 k-steps");
-    if constexpr (F) {
-        // head weights into LDS, then the samples and position encodings (beside the DMAs)
-        st.fx[st.tid] = p.wd[st.tid];
-        for (int e = st.tid; e < 384; e += 256) st.fx[256 + e] = p.wc[e];
-        fused_encode_p(p, st);
-        fused_encode_d(p, st.fx, st.tid, st.m0);
-    }
     // step 0's group (with the enc_p tile and the row maxima) landed, published to the block
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(dma_count(1, F) + dma_count(2, F) + dma_count(3, F)) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(dma_count(1) + dma_count(2) + dma_count(3)) : "memory");
     __syncthreads();
     const int rl = (st.tid >> 6) * 32 + st.sl;
-    st.er = row_exp(F ? fmaxf(st.lrp[rl], st.lrd[rl]) : st.lrp[rl]);
+    st.er = row_exp(st.lrp[rl]);
     enc_frags(st, rl);
 
-    chain_layer<0, F>(p, st);
-    chain_layer<1, F>(p, st);
-    chain_layer<2, F>(p, st);
-    chain_layer<3, F>(p, st);
-    chain_layer<4, F>(p, st);
-    chain_layer<5, F>(p, st);
-    chain_layer<6, F>(p, st);
-    chain_layer<7, F>(p, st);
-    chain_layer<8, F>(p, st);
-    chain_layer<9, F>(p, st);
+    chain_layer<0>(p, st);
+    chain_layer<1>(p, st);
+    chain_layer<2>(p, st);
+    chain_layer<3>(p, st);
+    chain_layer<4>(p, st);
+    chain_layer<5>(p, st);
+    chain_layer<6>(p, st);
+    chain_layer<7>(p, st);
+    chain_layer<8>(p, st);
+    chain_layer<9>(p, st);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every DMA landed before the LDS is released
-    if constexpr (F) {
-        __syncthreads();   // every row's raw4 in LDS
-        fused_composite<256>(p, st.fx, st.tid, st.m0);
-    }
     if (p.stamps && st.tid == 0) {
         unsigned long long* o = p.stamps + (size_t)blockIdx.x * 6;
         o[0] = st.t_wait; o[1] = st.t_bar; o[2] = st.t_mma; o[3] = st.t_epi;
@@ -765,8 +480,9 @@ __global__ __launch_bounds__(256) void k_mlp_chain_fwd(ChainFwdArgs p) {
 
 // ---------------------------------------------------------------------------
 // The chains at two waves per SIMD: the fused per-ray eval kernel (k_render_fused2, the
-// default of nerf_render_eval_fused), the training forward (k_mlp_chain_train2) and the
-// input-gradient chain (k_mlp_chain_bwd).  Same per-ray path as k_mlp_chain_fwd -- the ten
+// kernel of nerf_render_eval_fused), the training forward (k_mlp_chain_train2, and
+// k_mlp_chain_frozen without its saves) and the input-gradient chain (k_mlp_chain_bwd, and
+// k_mlp_chain_bwd_rays).  Same per-ray path as k_mlp_chain_fwd -- the ten
 // linears with the activations resident in registers, the weights streaming through an LDS
 // ring -- but a block's 128 rows are 8 waves x 16 rows on v_mfma_f32_16x16x32_f16: a wave's
 // accumulators (16 rows x 256 outputs) and its A operand (16 rows x 256 as fp16 pairs) are 64
@@ -791,6 +507,55 @@ __global__ __launch_bounds__(256) void k_mlp_chain_fwd(ChainFwdArgs p) {
 #ifndef NERF_CHAIN_STAMPS
 #define NERF_CHAIN_STAMPS 0   // diagnostic builds only (make EXTRA=-DNERF_CHAIN_STAMPS=1): phase stamps
 #endif
+
+// The schedule of a two-wave chain, computed once for the forward kernels (f2::Chain) and the
+// input-gradient kernels (b2::Chain) from a description D:
+//   NL, KS[NL]       layers and their 16-k steps (ring slot tt % NSLOT); a 32-k step is two
+//   NSLOT            ring slots; NSLOT / 2 slot pairs (32-k steps) in flight
+//   dma_count(tt)    vector-memory ops a wave issues for the DMAs of 16-k step tt
+//   pre_st(k)        stores a wave issues in 32-k step k before its barrier tile
+//   post_st(k)       ... and behind that tile's DMAs (zero in the forward chains)
+// The barrier of a 32-k step sits in the middle of the step before it.  32-k step k (global
+// over the chain, slot pair k % NPAIR) is published by barrier B_k, which every wave passes at
+// tile tb(k - 1) of step k - 1 (B_0 in the prologue) after waiting (vmcnt) for its own share of
+// step k's DMAs; right behind B_k a wave issues the DMAs of step k - 1 + NPAIR - 1 = k + NPAIR - 2
+// (the pair step k - 2 used: every wave is past it), and from tile tb + 1 on it reads step k's
+// first weight fragments while step k - 1's last MFMAs run.  A step therefore starts without a
+// barrier, without LDS latency and without DMA issue, and a layer's epilogue sits between two
+// barriers: the two waves of a SIMD leave it at their own pace (the older one first) and the
+// one ahead starts the next layer's MFMAs beside the other's epilogue VALU.
+template <class D> constexpr int nks(int l) { return D::KS[l] / 2; }
+template <class D> constexpr int kfirst(int l) { return l == 0 ? 0 : kfirst<D>(l - 1) + nks<D>(l - 1); }
+template <class D> constexpr int layer_of_k(int k) { int l = 0; while (l + 1 < D::NL && kfirst<D>(l + 1) <= k) ++l; return l; }
+// the first 16-k step of 32-k step k: every layer is a whole number of 32-k steps (nks)
+constexpr int tt_of_k(int k) { return 2 * k; }
+// vector-memory ops of the DMAs of 32-k step m (two 16-k steps), and of those issued in step j
+template <class D> constexpr int dma_step(int m) {
+    return m >= kfirst<D>(D::NL) ? 0 : D::dma_count(tt_of_k(m)) + D::dma_count(tt_of_k(m) + 1);
+}
+template <class D> constexpr int dma_in(int j) { return dma_step<D>(j + D::NSLOT / 2 - 1); }
+// the counted wait before B_{k+1} (at tile tb(k) of step k) for the DMAs of step k + 1, issued
+// behind B_{k + 3 - NPAIR} in step j0 = k + 2 - NPAIR (the prologue when negative): vmcnt counts
+// loads, stores and LDS-DMA together in issue order, so the count is every vector-memory op the
+// wave issued after them.  Ops left out of the count only make a wait stricter
+template <class D> constexpr int wait_n(int k) {
+    constexpr int P = D::NSLOT / 2;
+    const int j0 = k + 2 - P;
+    int n = 0;
+    if (j0 < 0)
+        for (int m = k + 2; m <= P - 2; ++m) n += dma_step<D>(m);
+    else
+        n += D::post_st(j0);
+    for (int j = (j0 + 1 > 0 ? j0 + 1 : 0); j < k; ++j) n += D::pre_st(j) + dma_in<D>(j) + D::post_st(j);
+    return n + D::pre_st(k);
+}
+// the prologue's wait for step 0 (it issues the DMAs of steps 0 .. NPAIR - 2)
+template <class D> constexpr int wait_prologue() {
+    int n = 0;
+    for (int m = 1; m <= D::NSLOT / 2 - 2; ++m) n += dma_step<D>(m);
+    return n;
+}
+
 namespace f2 {
 constexpr int NW = 8;                   // waves per block, two per SIMD
 constexpr int NTH = 64 * NW;            // threads
@@ -798,7 +563,13 @@ constexpr int SHALF = 256 * 16;         // one k-half of a slot: 256 image rows 
                                         // 16x16x32 fragment reads are conflict-free without a pad)
 constexpr int SPLANE = 2 * SHALF;
 constexpr int SBYTES = 2 * SPLANE;      // 16 KB per 16-k step (fp16 hi / lo planes)
+// the head region of LDS (State::fx), in floats
 constexpr int FX_WD = 0, FX_WC = 256;   // fc_density weight [256], fc_rgb weight [3][128]
+constexpr int FX_RAW = 640, FX_Z = 1152;   // raw4 [128][4] of the block's rows, eval: their sample depths [128]
+// eval: the view-direction encodings of the block's rays (27 values of encode_position L = 4,
+// official_nerf.py:87, 99-119, zero padded to 32) and their maxima, one 36-float record per
+// ray (fx + FX_ENCD): the view direction is per ray, so 128 / S records serve the block's rows
+constexpr int FX_ENCD = 1280, ENCD_REC = 36;
 
 // LDS map.  Eval: a 6-slot weight ring (two 32-k steps in flight) and the position-encoding
 // tile the prologue computes.  Training (TR): the encodings come from HBM, so their 32 KB go
@@ -857,20 +628,11 @@ constexpr int dma_count(int tt) {
     return tt >= CT ? 0 : (L_OUT[layer_of(tt)] == 256 ? 2 : 1) + (kbase(layer_of(tt)) == tt ? 1 : 0);
 }
 
-// The barrier of a 32-k step sits in the middle of the step before it.  32-k step k (global
-// over the chain, slot pair k % NPAIR) is published by barrier B_k, which every wave passes at
-// tile tb(k - 1) of step k - 1 (B_0 in the prologue) after waiting (vmcnt) for its own share of
-// step k's DMAs; right behind B_k a wave issues the DMAs of step k - 1 + NPAIR - 1 = k + NPAIR - 2
-// (the pair step k - 2 used: every wave is past it), and from tile tb + 1 on it reads step k's
-// first weight fragments while step k - 1's last MFMAs run.  A step therefore starts without a
-// barrier, without LDS latency and without DMA issue, and a layer's epilogue sits between two
-// barriers: the two waves of a SIMD leave it at their own pace (the older one first) and the
-// one ahead starts the next layer's MFMAs beside the other's epilogue VALU.
-constexpr int nks(int l) { return L_KS[l] / 2; }
-constexpr int kfirst(int l) { return l == 0 ? 0 : kfirst(l - 1) + nks(l - 1); }
-constexpr int layer_of_k(int k) { int l = 0; while (l + 1 < CNL && kfirst(l + 1) <= k) ++l; return l; }
-constexpr int tt_of_k(int k) { return kbase(layer_of_k(k)) + 2 * (k - kfirst(layer_of_k(k))); }
-constexpr int NK = kfirst(CNL);             // 32-k steps of the chain
+struct Steps {                              // the forward chains' k-step table (the schedule calculator's D)
+    static constexpr int NL = CNL;
+    static constexpr const int* KS = L_KS;
+};
+constexpr int NK = kfirst<Steps>(CNL);      // 32-k steps of the chain
 template <bool TR>
 constexpr int npair() { return LY<TR>::NSLOT / 2; }
 // weight fragments are read PF tiles ahead of their MFMAs (a ring of PF + 1 fragment pairs that
@@ -890,7 +652,7 @@ constexpr int PF_MAX = 4;                   // fragment-ring entries - 1 (State:
 static_assert(pf_tiles<true>() >= 1 && pf_tiles<true>() <= PF_MAX && pf_tiles<false>() >= 1 &&
                   pf_tiles<false>() <= PF_MAX && PF_BWD <= PF_MAX,
               "the weight-fragment ring holds PF_MAX + 1 entries");
-constexpr int ntj_k(int k) { return L_OUT[layer_of_k(k)] / 16; }
+constexpr int ntj_k(int k) { return L_OUT[layer_of_k<Steps>(k)] / 16; }
 // step -> first global tile and tile -> step, tabulated once (the templates ask per tile)
 struct TileMap {
     int first[NK + 1];
@@ -921,50 +683,6 @@ constexpr bool tb_ok() {
     return true;
 }
 static_assert(tb_ok(), "a step's barrier tile tb = ntj - PF - 1 must exist");
-// vector-memory ops of the DMAs of 32-k step m (two 16-k steps), and of those issued in step j
-constexpr int dma_step(int m) { return m >= NK ? 0 : dma_count(tt_of_k(m)) + dma_count(tt_of_k(m) + 1); }
-template <bool TR>
-constexpr int dma_in(int j) { return dma_step(j + npair<TR>() - 1); }
-// training, layer l >= 1, step u: the previous layer's output is saved two float4 stores per
-// tile pair (pairs 0 and 1 at u = 0, pair u + 1 at u = 1..6); at u = 0 of l >= 2 layer l - 2's
-// column maxima and ReLU words leave LDS (one store each).  All before the step's barrier.
-// SV = false (the frozen-field forward, k_mlp_chain_frozen): no output and no column-maximum
-// stores exist, only layer l - 2's ReLU words -- the counts must drop with the stores (a
-// count above the ops issued would let a wait pass before its DMAs landed)
-template <bool TR, bool SV = TR>
-constexpr int pre_st(int k) {
-    const int l = layer_of_k(k), u = k - kfirst(l);
-    if (!TR || l == 0) return 0;
-    if (!SV) return u == 0 && l >= 2 ? 1 : 0;
-    return u == 0 ? 4 + (l >= 2 ? 2 : 0) : (u <= 6 ? 2 : 0);
-}
-// the counted wait before B_{k+1} (at tile tb(k) of step k) for the DMAs of step k + 1, issued
-// behind B_{k + 3 - NPAIR} in step j0 = k + 2 - NPAIR (the prologue when negative): vmcnt counts
-// loads, stores and LDS-DMA together in issue order, so the count is every vector-memory op the
-// wave issued after them.  Ops left out of the count only make a wait stricter
-template <bool TR, bool SV = TR>
-constexpr int wait_n(int k) {
-    constexpr int P = npair<TR>();
-    const int j0 = k + 2 - P;
-    int n = 0;
-    if (j0 < 0)
-        for (int m = k + 2; m <= P - 2; ++m) n += dma_step(m);
-    for (int j = (j0 + 1 > 0 ? j0 + 1 : 0); j < k; ++j) n += pre_st<TR, SV>(j) + dma_in<TR>(j);
-    return n + pre_st<TR, SV>(k);
-}
-// the prologue's wait for step 0 (it issues the DMAs of steps 0 .. NPAIR - 2)
-template <bool TR>
-constexpr int wait_prologue() {
-    int n = 0;
-    for (int m = 1; m <= npair<TR>() - 2; ++m) n += dma_step(m);
-    return n;
-}
-static_assert(wait_n<true>(0) == dma_step(2) && wait_n<true>(1) == dma_in<true>(0), "training waits");
-static_assert(wait_n<true>(5) == pre_st<true>(4) + dma_in<true>(4) + pre_st<true>(5), "training waits");
-static_assert(wait_n<false>(0) == 0 && wait_n<false>(7) == 0, "eval waits");
-static_assert(wait_n<true, false>(0) == dma_step(2) && wait_n<true, false>(5) == dma_in<true>(4), "frozen waits");
-static_assert(wait_n<true, false>(10) == dma_in<true>(9) + 1, "frozen waits: l0's ReLU words leave at l2's first step");
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float pf2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -1094,12 +812,26 @@ __device__ __forceinline__ void write_stamps(const ChainFwdArgs& p, State& st) {
     }
 }
 
+// the wave's pieces of 16-k step s (of ks) of a chain image of ROWS rows into a ring slot: NP = 2
+// pieces cover image rows 0..255 (both planes, both k-halves), NP = 1 the 128 rows of the colour
+// layer.  A piece is 64 consecutive image rows of one plane and k-half: everything but the
+// lane's 16-byte offset is wave-uniform
+template <int ROWS, int ks, int s, int NP>
+__device__ __forceinline__ void dma_ring(const char* img, State& st, uint32_t slot) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int ph = NP == 2 ? (st.wave >> 2) + 2 * i : (st.wave >> 1);   // plane * 2 + k-half
+        const int n0 = NP == 2 ? 64 * (st.wave & 3) : 64 * (st.wave & 1);   // first image row
+        const int chunk = (ph >> 1) * (2 * ks) + 2 * s + (ph & 1);
+        dma16(img + (chunk * ROWS + n0) * 16, st.voff16, slot + ph * SHALF + n0 * 16);
+    }
+}
+
 // global 16-k step TT -> ring slot TT % NSLOT (2 pieces per wave; 1 for the 128-row colour
 // layer) + at a layer's first step one piece per wave: waves 0-3 the weight-row exponents
 // (64 image rows each), waves 4-7 the biases (16 lanes x 4 floats each); the 128-wide layer's
 // extra waves repeat the first ones (same bytes to the same place), so every wave issues the
-// same count (its vmcnt waits are compile-time).  A wave's piece is 64 consecutive image rows
-// of one plane and k-half: everything but the lane's 16-byte offset is wave-uniform
+// same count (its vmcnt waits are compile-time)
 template <int TT, bool TR>
 __device__ __forceinline__ void dma(const ChainFwdArgs& p, State& st) {
     using Y = LY<TR>;
@@ -1110,14 +842,7 @@ __device__ __forceinline__ void dma(const ChainFwdArgs& p, State& st) {
         constexpr int NO = L_OUT[l];
         const nerf_chain_layer& L = p.L[l];
         const char* img = reinterpret_cast<const char*>(L.img);
-        const uint32_t slot = st.lds0 + Y::O_RING + (TT % Y::NSLOT) * SBYTES;
-#pragma unroll
-        for (int i = 0; i < (NO == 256 ? 2 : 1); ++i) {
-            const int ph = NO == 256 ? (st.wave >> 2) + 2 * i : (st.wave >> 1);   // plane * 2 + k-half
-            const int n0 = NO == 256 ? 64 * (st.wave & 3) : 64 * (st.wave & 1);   // first image row
-            const int chunk = (ph >> 1) * (2 * ks) + 2 * s + (ph & 1);
-            dma16(img + (chunk * NO + n0) * 16, st.voff16, slot + ph * SHALF + n0 * 16);
-        }
+        dma_ring<NO, ks, s, NO == 256 ? 2 : 1>(img, st, st.lds0 + Y::O_RING + (TT % Y::NSLOT) * SBYTES);
         if constexpr (s == 0) {
             if (st.wave < 4) {
                 // the layer's weight-row exponents: the compact int array of the chain image
@@ -1136,11 +861,12 @@ __device__ __forceinline__ void dma(const ChainFwdArgs& p, State& st) {
     }
 }
 
-template <int T0, int N, bool TR>
-__device__ __forceinline__ void dma_n(const ChainFwdArgs& p, State& st) {
+// the DMAs of 16-k steps T0 .. T0 + N - 1 of chain D
+template <int T0, int N, class D, class P, class S>
+__device__ __forceinline__ void dma_n(const P& p, S& st) {
     if constexpr (N > 0) {
-        dma<T0, TR>(p, st);
-        dma_n<T0 + 1, N - 1, TR>(p, st);
+        D::template dma<T0>(p, st);
+        dma_n<T0 + 1, N - 1, D>(p, st);
     }
 }
 
@@ -1309,6 +1035,17 @@ static_assert(piece_tile<16>(P_STORE) <= 16 - 3 - 1 && piece_tile<16>(P0_STORE) 
                   piece_tile<16>(P_STORE_B) <= 16 - 3 - 1 && piece_tile<16>(P0_STORE_B) <= 16 - 3 - 1 &&
                   piece_tile<8>(P_STORE_B) <= 8 - 2 - 1 && piece_tile<8>(P0_STORE_B) <= 8 - 2 - 1,
               "stores before the barrier");
+// the lane's column-maximum words of tile 2 t + half (features 32 t + 16 half + 4 g ..), parity
+// par, in its copy of the Q at byte offset o_cmx of the block's LDS.  The offset is opaque per
+// call: the compiler would otherwise keep every piece's address live across the chain (the LDS
+// offsets of the arrays are beyond a ds_* immediate: they ride in the base)
+template <int Q>
+__device__ __forceinline__ uint32_t* cm_at(const State& st, int o_cmx, int par, int t, int half) {
+    int o = o_cmx + 16 * st.g + (Q == 1 ? 0 : 4 * CMS * (st.n >> (Q == 2 ? 3 : 2)));
+    asm volatile("" : "+v"(o));
+    return reinterpret_cast<uint32_t*>(st.lds + o) + par * 256 + 32 * t + 16 * half;
+}
+
 // training: the save work of layer l's k-step u (the previous layer's output, P = p.L[l - 1]),
 // piece j of ntj.  SV = false (frozen field): the ReLU words only -- no output store, no column maxima
 template <int l, int u, int j, int ntj, bool SV>
@@ -1318,16 +1055,9 @@ __device__ __forceinline__ void save_pieces(const ChainFwdArgs& p, State& st) {
         const nerf_chain_layer& P = p.L[l - 1];
         constexpr bool relu = l - 1 != 8;           // lf has no ReLU
         constexpr int par = (l - 1) & 1;
-        // a per-piece opaque copy of the lane's LDS offsets (the compiler would otherwise keep
-        // every piece's address live across the chain)
-        // (the LDS offsets of the arrays are beyond a ds_* immediate: they ride in the base)
         constexpr int Q = CMQ_FWD;
-        auto cm_at = [&](int t, int half) {
-            int o = Y::O_CMX + 16 * st.g + (Q == 1 ? 0 : 4 * CMS * (st.n >> (Q == 2 ? 3 : 2)));
-            asm volatile("" : "+v"(o));
-            return reinterpret_cast<uint32_t*>(st.lds + o) + par * 256 + 32 * t + 16 * half;
-        };
-        auto msk_at = [&](int t) {
+        auto cm = [&](int t, int half) { return cm_at<Q>(st, Y::O_CMX, par, t, half); };
+        auto msk_at = [&](int t) {   // (a per-piece opaque copy of the lane's LDS offset, as cm_at)
             int o = Y::O_MSK + 4 * MSKW * st.rl;
             asm volatile("" : "+v"(o));
             return reinterpret_cast<uint32_t*>(st.lds + o) + par * 128 * MSKW + t;
@@ -1338,8 +1068,8 @@ __device__ __forceinline__ void save_pieces(const ChainFwdArgs& p, State& st) {
         if constexpr (u == 0) {
             if constexpr (SV && j == piece_tile<ntj>(P0_STORE)) tile_store4<256>(ob, st.vrow, 0, st.xs[0]);
             if constexpr (SV && j == piece_tile<ntj>(P0_STORE_B)) tile_store4<256>(ob, st.vrow, 64, st.xs[1]);
-            if constexpr (CM && j == piece_tile<ntj>(P0_CMAX_A)) colmax4<Q>(st.xs[0], cm_at(0, 0), leader);
-            if constexpr (CM && j == piece_tile<ntj>(P0_CMAX_B)) colmax4<Q>(st.xs[1], cm_at(0, 1), leader);
+            if constexpr (CM && j == piece_tile<ntj>(P0_CMAX_A)) colmax4<Q>(st.xs[0], cm(0, 0), leader);
+            if constexpr (CM && j == piece_tile<ntj>(P0_CMAX_B)) colmax4<Q>(st.xs[1], cm(0, 1), leader);
             if constexpr (RW && j == piece_tile<ntj>(P0_RELU)) relu_put(msk_at(0), relu_word(st.act_hi[0], st), st);
         }
         if constexpr (u + 1 < 8) {
@@ -1347,37 +1077,34 @@ __device__ __forceinline__ void save_pieces(const ChainFwdArgs& p, State& st) {
             if constexpr (SV && j == piece_tile<ntj>(P_STORE)) tile_store4<256>(ob, st.vrow, 128 * t, st.xs[2 * t]);
             if constexpr (SV && j == piece_tile<ntj>(P_STORE_B))
                 tile_store4<256>(ob, st.vrow, 128 * t + 64, st.xs[2 * t + 1]);
-            if constexpr (CM && j == piece_tile<ntj>(P_CMAX_A)) colmax4<Q>(st.xs[2 * t], cm_at(t, 0), leader);
-            if constexpr (CM && j == piece_tile<ntj>(P_CMAX_B)) colmax4<Q>(st.xs[2 * t + 1], cm_at(t, 1), leader);
+            if constexpr (CM && j == piece_tile<ntj>(P_CMAX_A)) colmax4<Q>(st.xs[2 * t], cm(t, 0), leader);
+            if constexpr (CM && j == piece_tile<ntj>(P_CMAX_B)) colmax4<Q>(st.xs[2 * t + 1], cm(t, 1), leader);
             if constexpr (RW && j == piece_tile<ntj>(P_RELU)) relu_put(msk_at(t), relu_word(st.act_hi[t], st), st);
         }
     }
 }
 
-// the next k-step's A fragment (tiles 2 (u + 1), 2 (u + 1) + 1 of the previous epilogue), in
-// four pieces
-template <int l, int u, int j, int ntj>
-__device__ __forceinline__ void split_pieces(State& st) {
-    if constexpr (l > 0 && u + 1 < 8) {
-        constexpr int t = u + 1;
-        const f32x4 A = st.xs[2 * t], B = st.xs[2 * t + 1];
-        const float s = st.ser;
-        if constexpr (j == piece_tile<ntj>(P_SPLIT_HI_A)) {
-            st.act_hi[t].x = mhi(A[0], A[1], s);
-            st.act_hi[t].y = mhi(A[2], A[3], s);
-        }
-        if constexpr (j == piece_tile<ntj>(P_SPLIT_HI_B)) {
-            st.act_hi[t].z = mhi(B[0], B[1], s);
-            st.act_hi[t].w = mhi(B[2], B[3], s);
-        }
-        if constexpr (j == piece_tile<ntj>(P_SPLIT_LO_A)) {
-            st.act_lo[t].x = mlo(A[0], A[1], s, st.act_hi[t].x);
-            st.act_lo[t].y = mlo(A[2], A[3], s, st.act_hi[t].y);
-        }
-        if constexpr (j == piece_tile<ntj>(P_SPLIT_LO_B)) {
-            st.act_lo[t].z = mlo(B[0], B[1], s, st.act_hi[t].z);
-            st.act_lo[t].w = mlo(B[2], B[3], s, st.act_hi[t].w);
-        }
+// k-step t's A fragment (tiles 2 t, 2 t + 1 of the previous epilogue) in four pieces, behind
+// tile j of the k-step before it
+template <int t, int j, int ntj>
+__device__ __forceinline__ void split_pair(State& st) {
+    const f32x4 A = st.xs[2 * t], B = st.xs[2 * t + 1];
+    const float s = st.ser;
+    if constexpr (j == piece_tile<ntj>(P_SPLIT_HI_A)) {
+        st.act_hi[t].x = mhi(A[0], A[1], s);
+        st.act_hi[t].y = mhi(A[2], A[3], s);
+    }
+    if constexpr (j == piece_tile<ntj>(P_SPLIT_HI_B)) {
+        st.act_hi[t].z = mhi(B[0], B[1], s);
+        st.act_hi[t].w = mhi(B[2], B[3], s);
+    }
+    if constexpr (j == piece_tile<ntj>(P_SPLIT_LO_A)) {
+        st.act_lo[t].x = mlo(A[0], A[1], s, st.act_hi[t].x);
+        st.act_lo[t].y = mlo(A[2], A[3], s, st.act_hi[t].y);
+    }
+    if constexpr (j == piece_tile<ntj>(P_SPLIT_LO_B)) {
+        st.act_lo[t].z = mlo(B[0], B[1], s, st.act_hi[t].z);
+        st.act_lo[t].w = mlo(B[2], B[3], s, st.act_hi[t].w);
     }
 }
 
@@ -1385,24 +1112,24 @@ __device__ __forceinline__ void split_pieces(State& st) {
 // k-chunk g -- slot g >> 1 of the step's pair, k-half g & 1, image row 16 j + n -- one
 // ds_read_b128 per plane from the lane's base (two bases: slot pairs 0-1 and 2-3 of the ring)
 // with the rest an immediate offset
-template <int G, bool TR>
+// (D: the chain's ring depth PF + 1, slot count, ring offset and tile-to-step map)
+template <int G, class D>
 __device__ __forceinline__ void frag_read(State& st) {
-    if constexpr (G < NG) {
-        using Y = LY<TR>;
-        constexpr int R = pf_tiles<TR>() + 1;
-        constexpr int k = step_of_tile(G), j = G - gtile(k), slot = tt_of_k(k) % Y::NSLOT;
+    if constexpr (G < D::NG) {
+        constexpr int R = D::PF + 1;
+        constexpr int k = D::step_of_tile(G), j = G - D::gtile(k), slot = tt_of_k(k) % D::NSLOT;
         static_assert(slot % 2 == 0, "a 32-k step's two slots are consecutive");
-        constexpr int off = Y::O_RING + (slot & 3) * SBYTES + 256 * j;
+        constexpr int off = D::O_RING + (slot & 3) * SBYTES + 256 * j;
         const char* b = st.lds + st.fr + (slot >= 4 ? 4 * SBYTES : 0);
         st.wh[G % R] = *reinterpret_cast<const uint4*>(b + off);
         st.wl[G % R] = *reinterpret_cast<const uint4*>(b + off + SPLANE);
     }
 }
-template <int G0, int N, bool TR>
+template <int G0, int N, class D>
 __device__ __forceinline__ void frag_reads(State& st) {
     if constexpr (N > 0) {
-        frag_read<G0, TR>(st);
-        frag_reads<G0 + 1, N - 1, TR>(st);
+        frag_read<G0, D>(st);
+        frag_reads<G0 + 1, N - 1, D>(st);
     }
 }
 
@@ -1438,35 +1165,81 @@ __device__ __forceinline__ void layer_start(const ChainFwdArgs& p, State& st) {
     }
 }
 
-// tile j of 32-k step u of layer l: the read of tile j + PF's fragments, this tile's three
-// MFMA products, the pieces placed behind it, and at tile tb the wait, barrier B_{k+1} and the
-// DMAs of step k + NPAIR - 1 (one 16-k step at tb, the other at tb + 1)
-template <int l, int u, bool TR, bool SV, int j, int ntj>
-__device__ __forceinline__ void mstep_tiles(const ChainFwdArgs& p, State& st, const uint4& ah, const uint4& al) {
-    constexpr int PF = pf_tiles<TR>(), R = PF + 1;
-    constexpr int k = kfirst(l) + u, G = gtile(k) + j, T = tb<TR>(k);
+// The description of a forward chain (the schedule calculator's D, frag_read's ring, what
+// dma_n and tiles issue): TR the training forward, SV = false the frozen-field forward
+template <bool TR, bool SV = TR>
+struct Chain : Steps {
+    static constexpr int NSLOT = LY<TR>::NSLOT, O_RING = LY<TR>::O_RING;
+    static constexpr int PF = pf_tiles<TR>(), NG = f2::NG;
+    static constexpr int step_of_tile(int G) { return f2::step_of_tile(G); }
+    static constexpr int gtile(int k) { return f2::gtile(k); }
+    static constexpr int dma_count(int tt) { return f2::dma_count(tt); }
+    // training, layer l >= 1, step u: the previous layer's output is saved two float4 stores per
+    // tile pair (pairs 0 and 1 at u = 0, pair u + 1 at u = 1..6); at u = 0 of l >= 2 layer l - 2's
+    // column maxima and ReLU words leave LDS (one store each).  All before the step's barrier.
+    // SV = false (the frozen-field forward, k_mlp_chain_frozen): no output and no column-maximum
+    // stores exist, only layer l - 2's ReLU words -- the counts must drop with the stores (a
+    // count above the ops issued would let a wait pass before its DMAs landed)
+    static constexpr int pre_st(int k) {
+        const int l = layer_of_k<Steps>(k), u = k - kfirst<Steps>(l);
+        if (!TR || l == 0) return 0;
+        if (!SV) return u == 0 && l >= 2 ? 1 : 0;
+        return u == 0 ? 4 + (l >= 2 ? 2 : 0) : (u <= 6 ? 2 : 0);
+    }
+    static constexpr int post_st(int) { return 0; }
+    template <int TT>
+    static __device__ __forceinline__ void dma(const ChainFwdArgs& p, State& st) { f2::dma<TT, TR>(p, st); }
+    // behind tile j of layer l's k-step u: the steps from the register tile split the next step's
+    // A fragment and (training) save the previous layer's output
+    template <int l, int u, int j, int ntj>
+    static __device__ __forceinline__ void pieces(const ChainFwdArgs& p, State& st) {
+        if constexpr (u == 0 && j == 0) layer_start<l, TR, SV>(p, st);
+        if constexpr (l > 0 && u + 1 < 8) split_pair<u + 1, j, ntj>(st);
+        if constexpr (TR) save_pieces<l, u, j, ntj, SV>(p, st);
+    }
+    static __device__ __forceinline__ void tick(const ChainFwdArgs& p, State& st, unsigned long long* bucket) {
+        f2::tick(p, st, bucket);
+    }
+};
+using Train = Chain<true>;
+using Frozen = Chain<true, false>;
+using Eval = Chain<false>;
+static_assert(wait_n<Train>(0) == dma_step<Train>(2) && wait_n<Train>(1) == dma_in<Train>(0), "training waits");
+static_assert(wait_n<Train>(5) == Train::pre_st(4) + dma_in<Train>(4) + Train::pre_st(5), "training waits");
+static_assert(wait_n<Eval>(0) == 0 && wait_n<Eval>(7) == 0, "eval waits");
+static_assert(wait_n<Frozen>(0) == dma_step<Train>(2) && wait_n<Frozen>(5) == dma_in<Train>(4), "frozen waits");
+static_assert(wait_n<Frozen>(10) == dma_in<Train>(9) + 1, "frozen waits: l0's ReLU words leave at l2's first step");
+
+// tile j (of ntj) of 32-k step u of layer l of chain D: the read of tile j + PF's fragments, this
+// tile's three MFMA products, the pieces placed behind it (D::pieces), and at the barrier tile T
+// the wait, barrier B_{k+1} and the DMAs of step k + NPAIR - 1 (one 16-k step at T, the other at
+// T + DMA2)
+template <class D, int l, int u, int j, int ntj, class P, class S>
+__device__ __forceinline__ void tiles(const P& p, S& st, const uint4& ah, const uint4& al) {
+    constexpr int PF = D::PF, R = PF + 1, T = ntj - PF - 1;
+    constexpr int k = kfirst<D>(l) + u, G = D::gtile(k) + j;
+    constexpr bool more = k + 1 < kfirst<D>(D::NL);           // a step follows
+    constexpr int TN = tt_of_k(k + D::NSLOT / 2 - 1);         // ... and this step issues these DMAs
     if constexpr (j < ntj) {
         // the next layer's first tiles are read after this layer's epilogue (kstep): the ring
         // is not live across the epilogue's registers
-        if constexpr (G + PF < NG && layer_of_k(step_of_tile(G + PF)) == l) frag_read<G + PF, TR>(st);
+        if constexpr (G + PF < D::NG && layer_of_k<D>(D::step_of_tile(G + PF)) == l) frag_read<G + PF, D>(st);
         __builtin_amdgcn_sched_barrier(0);
         st.acc[j] = mfma16(st.wh[G % R], al, st.acc[j]);   // hi . lo
         st.acc[j] = mfma16(st.wl[G % R], ah, st.acc[j]);   // lo . hi
         st.acc[j] = mfma16(st.wh[G % R], ah, st.acc[j]);   // hi . hi
-        if constexpr (u == 0 && j == 0) layer_start<l, TR, SV>(p, st);
-        split_pieces<l, u, j, ntj>(st);
-        if constexpr (TR) save_pieces<l, u, j, ntj, SV>(p, st);
-        if constexpr (k + 1 < NK && j == T) {
-            tick(p, st, nullptr);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_n<TR, SV>(k)) : "memory");
-            tick(p, st, &st.t_wait);
+        D::template pieces<l, u, j, ntj>(p, st);
+        if constexpr (more && j == T) {
+            D::tick(p, st, nullptr);
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_n<D>(k)) : "memory");
+            D::tick(p, st, &st.t_wait);
             __syncthreads();
-            tick(p, st, &st.t_bar);
-            dma<tt_of_k(k + npair<TR>() - 1), TR>(p, st);
+            D::tick(p, st, &st.t_bar);
+            D::template dma<TN>(p, st);
         }
-        if constexpr (k + 1 < NK && j == T + DMA2) dma<tt_of_k(k + npair<TR>() - 1) + 1, TR>(p, st);
+        if constexpr (more && j == T + DMA2) D::template dma<TN + 1>(p, st);
         __builtin_amdgcn_sched_barrier(0);
-        mstep_tiles<l, u, TR, SV, j + 1, ntj>(p, st, ah, al);
+        tiles<D, l, u, j + 1, ntj>(p, st, ah, al);
     }
 }
 
@@ -1477,10 +1250,10 @@ template <int l, int u, bool TR, bool SV>
 __device__ __forceinline__ void kstep(const ChainFwdArgs& p, State& st) {
     constexpr int nact = l == 0 ? 0 : 8;         // k-steps from the register tile, then the encoding
     constexpr int ntj = L_OUT[l] / 16;
-    if constexpr (u == 0) frag_reads<gtile(kfirst(l)), pf_tiles<TR>(), TR>(st);   // published by B_k
+    if constexpr (u == 0) frag_reads<gtile(kfirst<Steps>(l)), pf_tiles<TR>(), Chain<TR, SV>>(st);   // published by B_k
     const uint4& ah = u < nact ? st.act_hi[u < nact ? u : 0] : st.enc_hi[u < nact ? 0 : u - nact];
     const uint4& al = u < nact ? st.act_lo[u < nact ? u : 0] : st.enc_lo[u < nact ? 0 : u - nact];
-    mstep_tiles<l, u, TR, SV, 0, ntj>(p, st, ah, al);
+    tiles<Chain<TR, SV>, l, u, 0, ntj>(p, st, ah, al);
 }
 
 template <int l, int u, bool TR, bool SV>
@@ -1592,7 +1365,7 @@ __device__ __forceinline__ void layer(const ChainFwdArgs& p, State& st) {
     if constexpr (l < CNL - 1) {
         // next layer's A operand: row exponent over the row's 256 features (and the encoding
         // the next layer joins), k-step 0's fp16 pairs now, the others during the next layer's
-        // k-steps (split_pieces)
+        // k-steps (split_pair)
         float m = rows_max(fmaxf(rmx, rmx1));
         const float* drec = st.fx + FX_ENCD + ENCD_REC * (st.rl / p.S);
         if constexpr (l == 3) {
@@ -1672,6 +1445,141 @@ __device__ __forceinline__ void encode_p(const ChainFwdArgs& p, State& st, const
     reinterpret_cast<float*>(st.lds + Y::O_RMX)[part * 128 + row] = m;
 }
 
+// the view-direction records (FX_ENCD) spread over threads t0 .. t0 + nt - 1 (nt a multiple of
+// 64): sixteen lanes (one DPP row) per ray, lane i < 12 one (level i / 3, coordinate i % 3) sin /
+// cos pair, lane 12 the direction itself, the record's max by a row reduction
+// the direction of the ray whose record lane u of the range works on in pass rb (zero past the
+// rays): loaded before the prologue's LDS-DMAs for pass 0
+__device__ __forceinline__ void encd_load(const ChainFwdArgs& p, int u, int nt, size_t m0, int rb, float (&d)[3]) {
+    const int nr = CROWS / p.S;
+    const int r = rb + (u >> 4);
+    const size_t ray = m0 / (size_t)p.S + r;
+    const bool live = u >= 0 && u < nt && r < nr && ray < (size_t)p.R;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[c] = live ? p.view[3 * ray + c] : 0.f;
+}
+__device__ __forceinline__ void fused_encode_d_rows(const ChainFwdArgs& p, float* fx, int tid, int t0, int nt,
+                                                    size_t m0, const float (&d0)[3]) {
+    const int nr = CROWS / p.S;
+    const int u = tid - t0;
+    if (u < 0 || u >= nt) return;
+    const int i = u & 15;
+    for (int rb = 0; rb < nr; rb += nt / 16) {   // block-uniform trip count: the row shuffles stay converged
+        const int r = rb + (u >> 4);
+        float dv[3] = {d0[0], d0[1], d0[2]};
+        if (rb > 0) encd_load(p, u, nt, m0, rb, dv);
+        float m = 0.f;
+        if (r < nr) {
+            float* rec = fx + FX_ENCD + ENCD_REC * r;
+            if (i < 12) {
+                const int lv = i / 3, c = i % 3;
+                const float d = c == 0 ? dv[0] : c == 1 ? dv[1] : dv[2];
+                float sn, cs;
+                sincosf((float)(1 << lv) * d, &sn, &cs);
+                rec[3 + 6 * lv + c] = sn;
+                rec[6 + 6 * lv + c] = cs;
+                m = fmaxf(fabsf(sn), fabsf(cs));
+            } else if (i == 12) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    rec[c] = dv[c];
+                    m = fmaxf(m, fabsf(dv[c]));
+                }
+            } else if (i == 13) {
+#pragma unroll
+                for (int c = 27; c < 32; ++c) rec[c] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        if (r < nr && i == 0) fx[FX_ENCD + ENCD_REC * r + 32] = m;
+    }
+}
+
+// eval epilogue: sigma -> alpha -> exclusive-product compositing of the block's 128 / S rays
+// (rendering.py:113-141), from the raw4 / z rows in LDS, with the arithmetic of
+// k_composite16_fwd (so the fused and the unfused render agree bit for bit): one 16-lane DPP
+// row per ray, lane l owning samples [l J, l J + J) (J = max(1, S / 16)); transmittance by a
+// row prefix-product scan, the sums by row butterflies; each lane stores its J alphas as
+// contiguous float4s (a ray's S alphas are one contiguous run across its row)
+template <int J, int NTH>
+__device__ __forceinline__ void fused_composite16(const ChainFwdArgs& p, const float* fx, int tid, size_t m0) {
+    const int S = p.S;
+    const int nr = CROWS / S;
+    const int l16 = tid & 15;
+    for (int rb = 0; rb < nr; rb += NTH / 16) {    // NTH / 16 rays per pass of the block
+        const int rloc = rb + (tid >> 4);
+        const size_t ray = m0 / (size_t)S + rloc;
+        const bool active = rloc < nr && ray < (size_t)p.R;   // whole 16-lane rows are (in)active
+        const int i0 = l16 * J;
+        float al[J], T[J], c[J][3], z[J];
+        bool valid[J];
+        float pl = 1.f;
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            const int i = i0 + j;
+            valid[j] = active && i < S;
+            float a = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, zz = 0.f;
+            if (valid[j]) {
+                const int e = rloc * S + i;
+                const float4 r = *reinterpret_cast<const float4*>(fx + FX_RAW + 4 * e);
+                zz = fx[FX_Z + e];
+                const float sg = f_density(r.x, p.flags);
+                if (p.flags & F_DIST_ALPHA)
+                    a = i == S - 1 ? 1.f : 1.f - __expf(-1.0f * sg * (fx[FX_Z + e + 1] - zz));   // rendering.py:116-122
+                else
+                    a = 1.f - __expf(-1.0f * sg);
+                c0 = f_sigmoid(r.y); c1 = f_sigmoid(r.z); c2 = f_sigmoid(r.w);
+            }
+            al[j] = a; z[j] = zz;
+            c[j][0] = c0; c[j][1] = c1; c[j][2] = c2;
+            T[j] = pl;
+            pl *= valid[j] ? (1.f - a + kEps) : 1.f;
+        }
+        const float excl = dpp_f<0x111>(1.f, row_scan_mul(pl));   // product over the lanes before this one
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, sd = 0.f, sw = 0.f;
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            const float w = al[j] * (T[j] * excl);
+            s0 += w * c[j][0];
+            s1 += w * c[j][1];
+            s2 += w * c[j][2];
+            sd += w * z[j];
+            sw += w;
+        }
+        float* ao = p.alpha + ray * (size_t)S + i0;
+        if (J % 4 == 0 && active) {
+#pragma unroll
+            for (int q = 0; q < J / 4; ++q)
+                *reinterpret_cast<float4*>(ao + 4 * q) = make_float4(al[4 * q], al[4 * q + 1], al[4 * q + 2], al[4 * q + 3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < J; ++j)
+                if (valid[j]) ao[j] = al[j];
+        }
+        s0 = row_sum(s0); s1 = row_sum(s1); s2 = row_sum(s2); sd = row_sum(sd);
+        if (p.flags & F_WHITE_BKGD) sw = row_sum(sw);
+        if (active && l16 == 0) {
+            if (p.flags & F_WHITE_BKGD) {          // rendering.py:139-141
+                const float bg = 1.f - sw;
+                s0 += bg; s1 += bg; s2 += bg;
+            }
+            p.rgb[3 * ray + 0] = s0;
+            p.rgb[3 * ray + 1] = s1;
+            p.rgb[3 * ray + 2] = s2;
+            p.dist[ray] = sd;
+        }
+    }
+}
+
+template <int NTH>
+__device__ __forceinline__ void fused_composite(const ChainFwdArgs& p, const float* fx, int tid, size_t m0) {
+    if (p.S >= 128) fused_composite16<8, NTH>(p, fx, tid, m0);
+    else if (p.S >= 64) fused_composite16<4, NTH>(p, fx, tid, m0);
+    else if (p.S >= 32) fused_composite16<2, NTH>(p, fx, tid, m0);
+    else fused_composite16<1, NTH>(p, fx, tid, m0);
+}
+
 // waves 4-7 (the second-dispatched half, the arbitration loser) at s_setprio 1 for the whole
 // chain (MI355X_MICROARCH.md "Two waves per SIMD" item 4): -0.5 % per cfg2 step in two
 // interleaved library A/Bs (profiles/r05/chain_variants_ab.txt)
@@ -1729,12 +1637,12 @@ __global__ __launch_bounds__(512, 2) void k_render_fused2(ChainFwdArgs p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (st.tid < 256) st.fx[FX_WD + st.tid] = wdv;
     if (st.tid < 384) st.fx[FX_WC + st.tid] = wcv;
-    dma_n<0, 2 * (npair<false>() - 1), false>(p, st);   // steps 0 .. NPAIR - 2
+    dma_n<0, 2 * (npair<false>() - 1), Eval>(p, st);   // steps 0 .. NPAIR - 2
     // the samples and both encodings beside the DMAs; the view records on waves 4-7 (the encode_p
     // parts with 6 sincos, not 9): no wave carries 12 sincos more than the others into B_0
     encode_p(p, st, x, z);
     fused_encode_d_rows(p, st.fx, st.tid, 256, 256, st.m0, dv);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_prologue<false>()) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_prologue<Eval>()) : "memory");
     __syncthreads();   // B_0 (and the encodings in LDS)
     {
         const float* rp = reinterpret_cast<const float*>(smem + Y::O_RMX);
@@ -1791,8 +1699,8 @@ __device__ __forceinline__ void chain_train_body(const ChainFwdArgs& p, char* sm
     static_assert(2 * 128 * MSKW == 4 * NTH, "one uint4 per thread");
     reinterpret_cast<uint4*>(smem + Y::O_MSK)[st.tid] = make_uint4(0u, 0u, 0u, 0u);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    dma_n<0, 2 * (npair<true>() - 1), true>(p, st);   // steps 0 .. NPAIR - 2
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_prologue<true>()) : "memory");
+    dma_n<0, 2 * (npair<true>() - 1), Train>(p, st);   // steps 0 .. NPAIR - 2
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_prologue<Train>()) : "memory");
     __syncthreads();   // B_0
     tick(p, st, &st.t_pro);
     chain_layers<true, SV>(p, st);
@@ -1857,60 +1765,15 @@ constexpr bool first_step(int tt) { return tt < CTB && kb(layer_of(tt)) == tt; }
 // (waves 0-3 the weight-row exponents, waves 4-7 the block's ReLU words of the layer input)
 constexpr int dma_count(int tt) { return tt >= CTB ? 0 : 2 + (first_step(tt) ? 1 : 0); }
 constexpr int NSLOT = 8, NPAIR = NSLOT / 2;   // ring slots (16-k), slot pairs (32-k steps)
-constexpr int nks(int i) { return KS_[i] / 2; }
-constexpr int kfirst(int i) { return i == 0 ? 0 : kfirst(i - 1) + nks(i - 1); }
-constexpr int layer_of_k(int k) { int i = 0; while (i + 1 < NL && kfirst(i + 1) <= k) ++i; return i; }
-constexpr int tt_of_k(int k) { return kb(layer_of_k(k)) + 2 * (k - kfirst(layer_of_k(k))); }
-constexpr int NK = kfirst(NL);
+struct Steps {                              // the k-step table (the schedule calculator's D)
+    static constexpr int NL = b2::NL;
+    static constexpr const int* KS = KS_;
+};
+constexpr int NK = kfirst<Steps>(NL);
 constexpr int PF = f2::PF_BWD;   // weight fragments read PF tiles ahead of their MFMAs (the ring runs across steps)
 constexpr int NG = 16 * NK;                  // MFMA tiles (16 per step)
 constexpr int TB = 16 - PF - 1;              // the barrier tile of a step (f2::tb)
-constexpr int dma_step(int m) { return m >= NK ? 0 : dma_count(tt_of_k(m)) + dma_count(tt_of_k(m) + 1); }
-constexpr int dma_in(int j) { return dma_step(j + NPAIR - 1); }
-// stores of step k before its barrier: the D_i pair stores (pairs 0 and 1 at u = 0, pair u + 1
-// at u = 1 .. nks - 2), at a layer's first step the previous dy's column maxima; behind its
-// DMAs (post): at a layer's last step the epilogue's row-max store.
-// RY = true (the ray-gradient chain, k_mlp_chain_bwd_rays): only D_0 and D_5 are stored by
-// k-steps (D_9 by the last epilogue), no column maxima, and of the epilogues' row maxima only
-// D_5's (layer 4's) -- the counts drop with the stores (f2::pre_st)
 constexpr bool ry_keeps(int d) { return d == 0 || d == 5 || d == 9; }   // the D_i the ray path consumes
-template <bool RY>
-constexpr int pre_st(int k) {
-    const int i = layer_of_k(k), u = k - kfirst(i);
-    const int pairs = u == 0 ? 4 : (u + 1 < nks(i) ? 2 : 0);
-    if (RY) return ry_keeps(i) ? pairs : 0;
-    return pairs + (u == 0 && i >= 1 ? 1 : 0);
-}
-template <bool RY>
-constexpr int post_st(int k) {
-    const int i = layer_of_k(k), u = k - kfirst(i);
-    return u == nks(i) - 1 && i < NL - 1 && (!RY || ry_keeps(i + 1)) ? 1 : 0;
-}
-// the counted wait before B_{k+1} for step k + 1's DMAs, issued behind the barrier of step j0 =
-// k + 2 - NPAIR (f2::wait_n, plus the post stores)
-template <bool RY>
-constexpr int wait_n(int k) {
-    const int j0 = k + 2 - NPAIR;
-    int n = 0;
-    if (j0 < 0)
-        for (int m = k + 2; m <= NPAIR - 2; ++m) n += dma_step(m);
-    else
-        n += post_st<RY>(j0);
-    for (int j = (j0 + 1 > 0 ? j0 + 1 : 0); j < k; ++j) n += pre_st<RY>(j) + dma_in(j) + post_st<RY>(j);
-    return n + pre_st<RY>(k);
-}
-constexpr int wait_prologue() {
-    int n = 0;
-    for (int m = 1; m <= NPAIR - 2; ++m) n += dma_step(m);
-    return n;
-}
-static_assert(wait_n<false>(0) == dma_step(2) + pre_st<false>(0) && wait_prologue() == dma_step(1) + dma_step(2),
-              "prologue waits");
-static_assert(wait_n<false>(4) == post_st<false>(2) + pre_st<false>(3) + dma_in(3) + post_st<false>(3) + pre_st<false>(4),
-              "waits");
-static_assert(wait_n<true>(0) == dma_step(2) + 4 && wait_n<true>(4) == pre_st<true>(3) + dma_in(3) && post_st<true>(3) == 0 &&
-                  wait_n<true>(8) == dma_in(7) && post_st<true>(kfirst(5) - 1) == 1 && pre_st<true>(kfirst(5)) == 4,
-              "ray-gradient chain waits");
 static_assert(f2::piece_tile<16>(f2::P_STORE) <= TB && f2::piece_tile<16>(f2::P0_STORE) <= TB &&
                   f2::piece_tile<16>(f2::P_STORE_B) <= TB && f2::piece_tile<16>(f2::P0_STORE_B) <= TB,
               "stores before B");
@@ -1937,14 +1800,7 @@ __device__ __forceinline__ void dma(const nerf_chain_bwd& p, State& st) {
         constexpr int ks = KS_[i];
         const char* img = reinterpret_cast<const char*>(p.wt_img[i]);
         constexpr int rows = KPB[i];   // image rows (checked by the host entry)
-        const uint32_t slot = st.lds0 + O_RING + (TT % NSLOT) * SBYTES;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int ph = (st.wave >> 2) + 2 * q;      // plane * 2 + k-half
-            const int n0 = 64 * (st.wave & 3);          // first image row of the wave's piece
-            const int chunk = (ph >> 1) * (2 * ks) + 2 * s + (ph & 1);
-            f2::dma16(img + (chunk * rows + n0) * 16, st.voff16, slot + ph * SHALF + n0 * 16);
-        }
+        f2::dma_ring<rows, ks, s, 2>(img, st, st.lds0 + O_RING + (TT % NSLOT) * SBYTES);
         if constexpr (s == 0) {
             if (st.wave < 4 || i == 0) {
                 // the weight-row exponents of image rows 0..255 (the layer's input features the
@@ -1965,13 +1821,6 @@ __device__ __forceinline__ void dma(const nerf_chain_bwd& p, State& st) {
         }
     }
 }
-template <int T0, int N>
-__device__ __forceinline__ void dma_n(const nerf_chain_bwd& p, State& st) {
-    if constexpr (N > 0) {
-        dma<T0>(p, st);
-        dma_n<T0 + 1, N - 1>(p, st);
-    }
-}
 
 // D_i's save work at layer i's k-step u, piece j: pair stores and the column maxima (parity
 // i & 1) of tiles 2t, 2t + 1 (pair 0 and 1 at u = 0, pair u + 1 later)
@@ -1982,11 +1831,7 @@ __device__ __forceinline__ void save_pieces(const nerf_chain_bwd& p, State& st) 
     constexpr bool ST = !RY || ry_keeps(i), CM = !RY;
     constexpr int W = i == 0 ? 128 : 256;   // D_0 = dyr is 128 wide
     constexpr int npair = W / 32;
-    auto cm_at = [&](int t, int half) {
-        int o = O_CMX + 16 * st.g + (CMQ == 1 ? 0 : 4 * f2::CMS * (st.n >> (CMQ == 2 ? 3 : 2)));
-        asm volatile("" : "+v"(o));
-        return reinterpret_cast<uint32_t*>(st.lds + o) + (i & 1) * 256 + 32 * t + 16 * half;
-    };
+    auto cm = [&](int t, int half) { return f2::cm_at<CMQ>(st, O_CMX, i & 1, t, half); };
     const bool leader = (st.n & (16 / CMQ - 1)) == 0;
     float* ob = ST ? p.dy[i] + st.m0 * W : nullptr;
     int vrow = st.vrow;
@@ -1994,62 +1839,16 @@ __device__ __forceinline__ void save_pieces(const nerf_chain_bwd& p, State& st) 
     if constexpr (u == 0) {
         if constexpr (ST && j == piece_tile<16>(f2::P0_STORE)) f2::tile_store4<W>(ob, vrow, 0, st.xs[0]);
         if constexpr (ST && j == piece_tile<16>(f2::P0_STORE_B)) f2::tile_store4<W>(ob, vrow, 64, st.xs[1]);
-        if constexpr (CM && j == piece_tile<16>(f2::P0_CMAX_A)) f2::colmax4<CMQ>(st.xs[0], cm_at(0, 0), leader);
-        if constexpr (CM && j == piece_tile<16>(f2::P0_CMAX_B)) f2::colmax4<CMQ>(st.xs[1], cm_at(0, 1), leader);
+        if constexpr (CM && j == piece_tile<16>(f2::P0_CMAX_A)) f2::colmax4<CMQ>(st.xs[0], cm(0, 0), leader);
+        if constexpr (CM && j == piece_tile<16>(f2::P0_CMAX_B)) f2::colmax4<CMQ>(st.xs[1], cm(0, 1), leader);
     }
     if constexpr (u + 1 < npair) {
         constexpr int t = u + 1;
         if constexpr (ST && j == piece_tile<16>(f2::P_STORE)) f2::tile_store4<W>(ob, vrow, 128 * t, st.xs[2 * t]);
         if constexpr (ST && j == piece_tile<16>(f2::P_STORE_B))
             f2::tile_store4<W>(ob, vrow, 128 * t + 64, st.xs[2 * t + 1]);
-        if constexpr (CM && j == piece_tile<16>(f2::P_CMAX_A)) f2::colmax4<CMQ>(st.xs[2 * t], cm_at(t, 0), leader);
-        if constexpr (CM && j == piece_tile<16>(f2::P_CMAX_B)) f2::colmax4<CMQ>(st.xs[2 * t + 1], cm_at(t, 1), leader);
-    }
-}
-
-template <int i, int u, int j>
-__device__ __forceinline__ void split_pieces(State& st) {
-    if constexpr (u + 1 < nks(i)) {
-        constexpr int t = u + 1;
-        const f2::f32x4 A = st.xs[2 * t], B = st.xs[2 * t + 1];
-        const float s = st.ser;
-        if constexpr (j == piece_tile<16>(f2::P_SPLIT_HI_A)) {
-            st.act_hi[t].x = f2::mhi(A[0], A[1], s);
-            st.act_hi[t].y = f2::mhi(A[2], A[3], s);
-        }
-        if constexpr (j == piece_tile<16>(f2::P_SPLIT_HI_B)) {
-            st.act_hi[t].z = f2::mhi(B[0], B[1], s);
-            st.act_hi[t].w = f2::mhi(B[2], B[3], s);
-        }
-        if constexpr (j == piece_tile<16>(f2::P_SPLIT_LO_A)) {
-            st.act_lo[t].x = f2::mlo(A[0], A[1], s, st.act_hi[t].x);
-            st.act_lo[t].y = f2::mlo(A[2], A[3], s, st.act_hi[t].y);
-        }
-        if constexpr (j == piece_tile<16>(f2::P_SPLIT_LO_B)) {
-            st.act_lo[t].z = f2::mlo(B[0], B[1], s, st.act_hi[t].z);
-            st.act_lo[t].w = f2::mlo(B[2], B[3], s, st.act_hi[t].w);
-        }
-    }
-}
-
-// global tile G's weight fragments into ring entry G % (PF + 1) (f2::frag_read)
-template <int G>
-__device__ __forceinline__ void frag_read(State& st) {
-    if constexpr (G < NG) {
-        constexpr int R = PF + 1;
-        constexpr int k = G / 16, j = G % 16, slot = tt_of_k(k) % NSLOT;
-        static_assert(slot % 2 == 0, "a 32-k step's two slots are consecutive");
-        constexpr int off = O_RING + (slot & 3) * SBYTES + 256 * j;
-        const char* b = st.lds + st.fr + (slot >= 4 ? 4 * SBYTES : 0);
-        st.wh[G % R] = *reinterpret_cast<const uint4*>(b + off);
-        st.wl[G % R] = *reinterpret_cast<const uint4*>(b + off + SPLANE);
-    }
-}
-template <int G0, int N>
-__device__ __forceinline__ void frag_reads(State& st) {
-    if constexpr (N > 0) {
-        frag_read<G0>(st);
-        frag_reads<G0 + 1, N - 1>(st);
+        if constexpr (CM && j == piece_tile<16>(f2::P_CMAX_A)) f2::colmax4<CMQ>(st.xs[2 * t], cm(t, 0), leader);
+        if constexpr (CM && j == piece_tile<16>(f2::P_CMAX_B)) f2::colmax4<CMQ>(st.xs[2 * t + 1], cm(t, 1), leader);
     }
 }
 
@@ -2076,39 +1875,62 @@ __device__ __forceinline__ void layer_start(const nerf_chain_bwd& p, State& st) 
     }
 }
 
-template <int i, int u, int j, bool RY>
-__device__ __forceinline__ void tiles(const nerf_chain_bwd& p, State& st, const uint4& ah, const uint4& al) {
-    constexpr int R = PF + 1;
-    constexpr int k = kfirst(i) + u, G = 16 * k + j;
-    if constexpr (j < 16) {
-        if constexpr (G + PF < NG && layer_of_k((G + PF) / 16) == i) frag_read<G + PF>(st);   // (f2::mstep_tiles)
-        __builtin_amdgcn_sched_barrier(0);
-        st.acc[j] = f2::mfma16(st.wh[G % R], al, st.acc[j]);   // hi . lo
-        st.acc[j] = f2::mfma16(st.wl[G % R], ah, st.acc[j]);   // lo . hi
-        st.acc[j] = f2::mfma16(st.wh[G % R], ah, st.acc[j]);   // hi . hi
-        if constexpr (u == 0 && j == 0) layer_start<i, RY>(p, st);
-        split_pieces<i, u, j>(st);
-        save_pieces<i, u, j, RY>(p, st);
-        if constexpr (k + 1 < NK && j == TB) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_n<RY>(k)) : "memory");
-            __syncthreads();   // B_{k+1}
-            dma<tt_of_k(k + NPAIR - 1)>(p, st);
-        }
-        if constexpr (k + 1 < NK && j == TB + f2::DMA2) dma<tt_of_k(k + NPAIR - 1) + 1>(p, st);
-        __builtin_amdgcn_sched_barrier(0);
-        tiles<i, u, j + 1, RY>(p, st, ah, al);
+// The description of an input-gradient chain (the schedule calculator's D, f2::frag_read's ring,
+// what f2::dma_n and f2::tiles issue).  RY = true (the ray-gradient chain, k_mlp_chain_bwd_rays):
+// only D_0 and D_5 are stored by k-steps (D_9 by the last epilogue), no column maxima, and of the
+// epilogues' row maxima only D_5's (layer 4's) -- the counts drop with the stores
+// (f2::Chain::pre_st)
+template <bool RY>
+struct Chain : Steps {
+    static constexpr int NSLOT = b2::NSLOT, O_RING = b2::O_RING, PF = b2::PF, NG = b2::NG;
+    static constexpr int step_of_tile(int G) { return G / 16; }
+    static constexpr int gtile(int k) { return 16 * k; }
+    static constexpr int dma_count(int tt) { return b2::dma_count(tt); }
+    // stores of step k before its barrier: the D_i pair stores (pairs 0 and 1 at u = 0, pair u + 1
+    // at u = 1 .. nks - 2), at a layer's first step the previous dy's column maxima
+    static constexpr int pre_st(int k) {
+        const int i = layer_of_k<Steps>(k), u = k - kfirst<Steps>(i);
+        const int pairs = u == 0 ? 4 : (u + 1 < nks<Steps>(i) ? 2 : 0);
+        if (RY) return ry_keeps(i) ? pairs : 0;
+        return pairs + (u == 0 && i >= 1 ? 1 : 0);
     }
-}
+    // ... and behind its DMAs: at a layer's last step the epilogue's row-max store
+    static constexpr int post_st(int k) {
+        const int i = layer_of_k<Steps>(k), u = k - kfirst<Steps>(i);
+        return u == nks<Steps>(i) - 1 && i < NL - 1 && (!RY || ry_keeps(i + 1)) ? 1 : 0;
+    }
+    template <int TT>
+    static __device__ __forceinline__ void dma(const nerf_chain_bwd& p, State& st) { b2::dma<TT>(p, st); }
+    // behind tile j of layer i's k-step u: the next step's A fragment, D_i's saves
+    template <int i, int u, int j, int ntj>
+    static __device__ __forceinline__ void pieces(const nerf_chain_bwd& p, State& st) {
+        if constexpr (u == 0 && j == 0) layer_start<i, RY>(p, st);
+        if constexpr (u + 1 < nks<Steps>(i)) f2::split_pair<u + 1, j, ntj>(st);
+        save_pieces<i, u, j, RY>(p, st);
+    }
+    static __device__ __forceinline__ void tick(const nerf_chain_bwd&, State&, unsigned long long*) {}
+};
+using Full = Chain<false>;
+using Rays = Chain<true>;
+static_assert(wait_n<Full>(0) == dma_step<Full>(2) + Full::pre_st(0) &&
+                  wait_prologue<Full>() == dma_step<Full>(1) + dma_step<Full>(2),
+              "prologue waits");
+static_assert(wait_n<Full>(4) == Full::post_st(2) + Full::pre_st(3) + dma_in<Full>(3) + Full::post_st(3) + Full::pre_st(4),
+              "waits");
+static_assert(wait_n<Rays>(0) == dma_step<Rays>(2) + 4 && wait_n<Rays>(4) == Rays::pre_st(3) + dma_in<Rays>(3) &&
+                  Rays::post_st(3) == 0 && wait_n<Rays>(8) == dma_in<Rays>(7) &&
+                  Rays::post_st(kfirst<Steps>(5) - 1) == 1 && Rays::pre_st(kfirst<Steps>(5)) == 4,
+              "ray-gradient chain waits");
 
 template <int i, int u, bool RY>
 __device__ __forceinline__ void kstep(const nerf_chain_bwd& p, State& st) {
-    if constexpr (u == 0) frag_reads<16 * kfirst(i), PF>(st);
-    tiles<i, u, 0, RY>(p, st, st.act_hi[u], st.act_lo[u]);
+    if constexpr (u == 0) f2::frag_reads<16 * kfirst<Steps>(i), PF, Chain<RY>>(st);
+    f2::tiles<Chain<RY>, i, u, 0, 16>(p, st, st.act_hi[u], st.act_lo[u]);
 }
 
 template <int i, int u, bool RY>
 __device__ __forceinline__ void ksteps(const nerf_chain_bwd& p, State& st) {
-    if constexpr (u < nks(i)) {
+    if constexpr (u < nks<Steps>(i)) {
         kstep<i, u, RY>(p, st);
         ksteps<i, u + 1, RY>(p, st);
     }
@@ -2262,8 +2084,8 @@ __device__ __forceinline__ void chain_bwd_body(const nerf_chain_bwd& p, char* sm
     f2::split_hi<0>(st);
     f2::split_lo<0>(st);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    dma_n<0, 2 * (NPAIR - 1)>(p, st);   // steps 0 .. NPAIR - 2
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_prologue()) : "memory");
+    f2::dma_n<0, 2 * (NPAIR - 1), Chain<RY>>(p, st);   // steps 0 .. NPAIR - 2
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(wait_prologue<Chain<RY>>()) : "memory");
     __syncthreads();   // B_0
     layers<RY>(p, st);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2293,6 +2115,91 @@ using namespace nerf;
 
 static unsigned long long* g_chain_stamps = nullptr;
 
+namespace {
+
+// How a forward entry takes the ten nerf_chain_layer descriptors: the chain images (exactly
+// L_OUT[l] rows) or the plain ones (at least), and whether it writes each layer's output, ReLU
+// words and column maxima.  Where it does, the feature layer still has no ReLU words and the
+// colour layer no column maxima.
+enum Need { FORBIDDEN, OPTIONAL, MANDATORY };
+struct DescMode {
+    bool chain_img;
+    Need out, mask, cmax;
+};
+
+// checks the descriptors under mode m and copies them into a.L; fn is the public entry's name
+int chain_layers_checked(const char* fn, const nerf_chain_layer* layers, const DescMode& m, ChainFwdArgs& a) {
+    for (int l = 0; l < CNL; ++l) {
+        const nerf_chain_layer& L = layers[l];
+        NERF_CHECK(L.img && L.bias, "%s: layer %d needs its weight image and bias", fn, l);
+        if (m.chain_img) {
+            NERF_CHECK((((uintptr_t)L.bias) & 15u) == 0 && (((uintptr_t)L.img) & 15u) == 0 && L.img_rows == L_OUT[l],
+                       "%s: layer %d: image / bias not 16-byte aligned or chain image rows %d != %d", fn, l,
+                       L.img_rows, L_OUT[l]);
+        } else {
+            NERF_CHECK((((uintptr_t)L.bias) & 15u) == 0, "%s: layer %d: bias not 16-byte aligned (16-byte LDS-DMA)", fn, l);
+            NERF_CHECK(L.img_rows >= L_OUT[l] && (((uintptr_t)L.img) & 15u) == 0,
+                       "%s: layer %d: image rows %d < %d or image not 16-byte aligned", fn, l, L.img_rows, L_OUT[l]);
+        }
+        // a pointer the kernel does not write would stay unwritten
+        if (m.out == FORBIDDEN && m.mask == FORBIDDEN)
+            NERF_CHECK(L.out == nullptr && L.mask == nullptr && L.cmax == nullptr,
+                       "%s: layer %d: the eval render saves no activations, masks or column maxima", fn, l);
+        else if (m.out == FORBIDDEN)
+            NERF_CHECK(L.out == nullptr && L.cmax == nullptr,
+                       "%s: layer %d: the frozen-field chain saves no layer output and no column maxima (out and cmax "
+                       "must be NULL)", fn, l);
+        // mandatory saves: the k-steps' vmcnt waits count their stores at compile time
+        if (m.out == MANDATORY)
+            NERF_CHECK(L.out && L.ldo == L_OUT[l] && (((uintptr_t)L.out) & 15u) == 0,
+                       "%s: layer %d: the training chain saves every layer output (ldo %d: 256 for l0..lf, 128 for the "
+                       "colour layer)", fn, l, L.ldo);
+        else if (m.out == OPTIONAL)
+            NERF_CHECK(L.out == nullptr || (L.ldo >= L_OUT[l] && L.ldo % 4 == 0 && (((uintptr_t)L.out) & 15u) == 0),
+                       "%s: layer %d: bad output (ldo %d)", fn, l, L.ldo);
+        if (m.mask == MANDATORY) {
+            NERF_CHECK(l == 8 || (L.mask && L.ldmask >= L_OUT[l] / 32 && L.ldmask % 2 == 0 &&
+                                  (((uintptr_t)L.mask) & 7u) == 0),
+                       "%s: layer %d: the ReLU words are mandatory (ldmask %d, even, 8-byte aligned)", fn, l, L.ldmask);
+            NERF_CHECK(l != 8 || L.mask == nullptr, "%s: the feature layer has no ReLU", fn);
+        } else if (m.mask == OPTIONAL) {
+            NERF_CHECK(L.mask == nullptr || L.ldmask >= L_OUT[l] / 32, "%s: layer %d: ldmask %d", fn, l, L.ldmask);
+        }
+        if (m.cmax == MANDATORY)
+            NERF_CHECK(l == CNL - 1 ? L.cmax == nullptr : L.cmax != nullptr,
+                       "%s: layer %d: column maxima are mandatory for l0..lf and absent for the colour layer", fn, l);
+        else if (m.cmax == OPTIONAL)
+            NERF_CHECK(l != CNL - 1 || L.cmax == nullptr, "%s: the colour layer has no column maxima", fn);
+        a.L[l] = L;
+    }
+    return NERF_OK;
+}
+
+// the checks nerf_mlp_chain_bwd and nerf_mlp_chain_bwd_rays share; fn is the public entry's name
+int chain_bwd_checked(const char* fn, const nerf_chain_bwd& p, bool scratch) {
+    NERF_CHECK(p.n_pad > 0 && p.n_pad % CROWS == 0, "%s: n_pad=%d must be a positive multiple of %d", fn, p.n_pad, CROWS);
+    NERF_CHECK(gemm_precision() == 2, "%s: the chain runs in GEMM precision mode 2 (fp16 pair images)", fn);
+    if (scratch)
+        NERF_CHECK(p.graw4 && p.hr_mask && p.ld_hr_mask >= 4 && p.wd && p.wc && p.scratch,
+                   "%s: graw4, the colour layer's ReLU words (ld >= 4), wd, wc and a scratch row are required", fn);
+    else
+        NERF_CHECK(p.graw4 && p.hr_mask && p.ld_hr_mask >= 4 && p.wd && p.wc,
+                   "%s: graw4, the colour layer's ReLU words (ld >= 4), wd and wc are required", fn);
+    NERF_CHECK((((uintptr_t)p.graw4) & 15u) == 0, "%s: pointer '%s' not 16-byte aligned", fn, "p.graw4");
+    NERF_CHECK((((uintptr_t)p.wd) & 15u) == 0, "%s: pointer '%s' not 16-byte aligned", fn, "p.wd");
+    NERF_CHECK((((uintptr_t)p.hr_mask) & 15u) == 0 && p.ld_hr_mask % 4 == 0, "%s: hr_mask 16-byte rows", fn);
+    for (int i = 0; i < 9; ++i) {
+        NERF_CHECK(p.wt_img[i] && (((uintptr_t)p.wt_img[i]) & 15u) == 0 && p.wt_img_rows[i] == b2::KPB[i],
+                   "%s: layer %d: weight-transpose chain image missing, unaligned or not %d rows", fn, i, b2::KPB[i]);
+        NERF_CHECK(i == 0 || (p.in_mask[i] && p.ld_in_mask[i] >= 8 && (((uintptr_t)p.in_mask[i]) & 15u) == 0 &&
+                              p.ld_in_mask[i] % 4 == 0),
+                   "%s: layer %d: the input's ReLU words (ld >= 8, 16-byte rows) are required", fn, i);
+    }
+    return NERF_OK;
+}
+
+}  // namespace
+
 extern "C" int nerf_mlp_chain_fwd(const float* enc_p, const float* enc_d, const float* enc_p_rmax,
                                   const float* enc_d_rmax, int n_pad, const nerf_chain_layer* layers, void* stream) {
     NERF_CHECK_PTR(enc_p); NERF_CHECK_PTR(enc_d); NERF_CHECK_PTR(enc_p_rmax); NERF_CHECK_PTR(enc_d_rmax);
@@ -2303,19 +2210,7 @@ extern "C" int nerf_mlp_chain_fwd(const float* enc_p, const float* enc_d, const 
     NERF_CHECK_ALIGN16(enc_p); NERF_CHECK_ALIGN16(enc_d);
     ChainFwdArgs a{};
     a.enc_p = enc_p; a.enc_d = enc_d; a.rp = enc_p_rmax; a.rd = enc_d_rmax; a.n_pad = n_pad;
-    for (int l = 0; l < CNL; ++l) {
-        const nerf_chain_layer& L = layers[l];
-        NERF_CHECK(L.img && L.bias, "%s: layer %d needs its weight image and bias", __func__, l);
-        NERF_CHECK((((uintptr_t)L.bias) & 15u) == 0, "%s: layer %d: bias not 16-byte aligned (16-byte LDS-DMA)",
-                   __func__, l);
-        NERF_CHECK(L.img_rows >= L_OUT[l] && (((uintptr_t)L.img) & 15u) == 0,
-                   "%s: layer %d: image rows %d < %d or image not 16-byte aligned", __func__, l, L.img_rows, L_OUT[l]);
-        NERF_CHECK(L.out == nullptr || (L.ldo >= L_OUT[l] && L.ldo % 4 == 0 && (((uintptr_t)L.out) & 15u) == 0),
-                   "%s: layer %d: bad output (ldo %d)", __func__, l, L.ldo);
-        NERF_CHECK(L.mask == nullptr || L.ldmask >= L_OUT[l] / 32, "%s: layer %d: ldmask %d", __func__, l, L.ldmask);
-        NERF_CHECK(l != CNL - 1 || L.cmax == nullptr, "%s: the colour layer has no column maxima", __func__);
-        a.L[l] = L;
-    }
+    if (const int rc = chain_layers_checked(__func__, layers, {false, OPTIONAL, OPTIONAL, OPTIONAL}, a)) return rc;
     a.stamps = g_chain_stamps;
     hipLaunchKernelGGL(k_mlp_chain_fwd<false>, dim3(n_pad / CROWS), dim3(256), 0, as_stream(stream), a);
     return check_launch(__func__);
@@ -2333,24 +2228,7 @@ extern "C" int nerf_mlp_chain_train(const float* enc_p, const float* enc_d, cons
     NERF_CHECK_ALIGN16(enc_p); NERF_CHECK_ALIGN16(enc_d); NERF_CHECK_ALIGN16(raw4);
     ChainFwdArgs a{};
     a.enc_p = enc_p; a.enc_d = enc_d; a.rp = enc_p_rmax; a.rd = enc_d_rmax; a.n_pad = n_pad;
-    for (int l = 0; l < CNL; ++l) {
-        const nerf_chain_layer& L = layers[l];
-        NERF_CHECK(L.img && L.bias, "%s: layer %d needs its weight image and bias", __func__, l);
-        NERF_CHECK((((uintptr_t)L.bias) & 15u) == 0 && (((uintptr_t)L.img) & 15u) == 0 && L.img_rows == L_OUT[l],
-                   "%s: layer %d: image / bias not 16-byte aligned or chain image rows %d != %d", __func__, l,
-                   L.img_rows, L_OUT[l]);
-        // every output is mandatory: the k-steps' vmcnt waits count these stores at compile time
-        NERF_CHECK(L.out && L.ldo == L_OUT[l] && (((uintptr_t)L.out) & 15u) == 0,
-                   "%s: layer %d: the training chain saves every layer output (ldo %d: 256 for l0..lf, 128 for the "
-                   "colour layer)", __func__, l, L.ldo);
-        NERF_CHECK(l == 8 || (L.mask && L.ldmask >= L_OUT[l] / 32 && L.ldmask % 2 == 0 &&
-                              (((uintptr_t)L.mask) & 7u) == 0),
-                   "%s: layer %d: the ReLU words are mandatory (ldmask %d, even, 8-byte aligned)", __func__, l, L.ldmask);
-        NERF_CHECK(l != 8 || L.mask == nullptr, "%s: the feature layer has no ReLU", __func__);
-        NERF_CHECK(l == CNL - 1 ? L.cmax == nullptr : L.cmax != nullptr,
-                   "%s: layer %d: column maxima are mandatory for l0..lf and absent for the colour layer", __func__, l);
-        a.L[l] = L;
-    }
+    if (const int rc = chain_layers_checked(__func__, layers, {true, MANDATORY, MANDATORY, MANDATORY}, a)) return rc;
     a.wd = wd; a.bd = bd; a.wc = wc; a.bc = bc; a.raw4 = raw4;
     a.stamps = g_chain_stamps;
     // algorithmic work per row: the ten linears over their unpadded inputs (63, 256 x 3, 319,
@@ -2372,28 +2250,11 @@ extern "C" int nerf_mlp_chain_frozen(const float* enc_p, const float* enc_d, con
     NERF_CHECK_PTR(raw4);
     NERF_CHECK(n_pad > 0 && n_pad % CROWS == 0, "%s: n_pad=%d must be a positive multiple of %d", __func__, n_pad,
                CROWS);
-    // the kernel has no output or column-maximum stores: a pointer given here would stay unwritten
-    for (int l = 0; l < CNL; ++l)
-        NERF_CHECK(layers[l].out == nullptr && layers[l].cmax == nullptr,
-                   "%s: layer %d: the frozen-field chain saves no layer output and no column maxima (out and cmax "
-                   "must be NULL)", __func__, l);
     NERF_CHECK(gemm_precision() == 2, "%s: the fused chain runs in GEMM precision mode 2 (fp16 pair images)", __func__);
     NERF_CHECK_ALIGN16(enc_p); NERF_CHECK_ALIGN16(enc_d); NERF_CHECK_ALIGN16(raw4);
     ChainFwdArgs a{};
     a.enc_p = enc_p; a.enc_d = enc_d; a.rp = enc_p_rmax; a.rd = enc_d_rmax; a.n_pad = n_pad;
-    for (int l = 0; l < CNL; ++l) {
-        const nerf_chain_layer& L = layers[l];
-        NERF_CHECK(L.img && L.bias, "%s: layer %d needs its weight image and bias", __func__, l);
-        NERF_CHECK((((uintptr_t)L.bias) & 15u) == 0 && (((uintptr_t)L.img) & 15u) == 0 && L.img_rows == L_OUT[l],
-                   "%s: layer %d: image / bias not 16-byte aligned or chain image rows %d != %d", __func__, l,
-                   L.img_rows, L_OUT[l]);
-        // the ReLU-word stores are counted in the k-steps' vmcnt waits at compile time
-        NERF_CHECK(l == 8 || (L.mask && L.ldmask >= L_OUT[l] / 32 && L.ldmask % 2 == 0 &&
-                              (((uintptr_t)L.mask) & 7u) == 0),
-                   "%s: layer %d: the ReLU words are mandatory (ldmask %d, even, 8-byte aligned)", __func__, l, L.ldmask);
-        NERF_CHECK(l != 8 || L.mask == nullptr, "%s: the feature layer has no ReLU", __func__);
-        a.L[l] = L;
-    }
+    if (const int rc = chain_layers_checked(__func__, layers, {true, FORBIDDEN, MANDATORY, FORBIDDEN}, a)) return rc;
     a.wd = wd; a.bd = bd; a.wc = wc; a.bc = bc; a.raw4 = raw4;
     a.stamps = g_chain_stamps;
     // the work of nerf_mlp_chain_train; HBM: the two encodings read, the ReLU words and raw4 written
@@ -2422,16 +2283,7 @@ extern "C" int nerf_render_eval_fused(const float* pts_o, const float* pts_d, co
     ChainFwdArgs a{};
     const int64_t n = (int64_t)n_rays * n_samples;
     a.n_pad = (int)((n + CROWS - 1) / CROWS * CROWS);
-    for (int l = 0; l < CNL; ++l) {
-        const nerf_chain_layer& L = layers[l];
-        NERF_CHECK(L.img && L.bias, "%s: layer %d needs its weight image and bias", __func__, l);
-        NERF_CHECK((((uintptr_t)L.bias) & 15u) == 0 && (((uintptr_t)L.img) & 15u) == 0 && L.img_rows == L_OUT[l],
-                   "%s: layer %d: image / bias not 16-byte aligned or chain image rows %d != %d", __func__, l,
-                   L.img_rows, L_OUT[l]);
-        NERF_CHECK(L.out == nullptr && L.mask == nullptr && L.cmax == nullptr,
-                   "%s: layer %d: the eval render saves no activations, masks or column maxima", __func__, l);
-        a.L[l] = L;
-    }
+    if (const int rc = chain_layers_checked(__func__, layers, {true, FORBIDDEN, FORBIDDEN, FORBIDDEN}, a)) return rc;
     a.po = pts_o; a.pd = pts_d; a.view = view;
     a.R = n_rays; a.S = n_samples; a.flags = flags; a.near_z = near_z; a.far_z = far_z;
     a.wd = wd; a.bd = bd; a.wc = wc; a.bc = bc;
@@ -2454,21 +2306,7 @@ extern "C" int nerf_chain_stamps_built(void) { return NERF_CHAIN_STAMPS; }
 extern "C" int nerf_mlp_chain_bwd(const nerf_chain_bwd* a, void* stream) {
     NERF_CHECK_PTR(a);
     const nerf_chain_bwd& p = *a;
-    NERF_CHECK(p.n_pad > 0 && p.n_pad % CROWS == 0, "%s: n_pad=%d must be a positive multiple of %d", __func__,
-               p.n_pad, CROWS);
-    NERF_CHECK(gemm_precision() == 2, "%s: the chain runs in GEMM precision mode 2 (fp16 pair images)", __func__);
-    NERF_CHECK(p.graw4 && p.hr_mask && p.ld_hr_mask >= 4 && p.wd && p.wc && p.scratch,
-               "%s: graw4, the colour layer's ReLU words (ld >= 4), wd, wc and a scratch row are required", __func__);
-    NERF_CHECK_ALIGN16(p.graw4); NERF_CHECK_ALIGN16(p.wd);
-    NERF_CHECK((((uintptr_t)p.hr_mask) & 15u) == 0 && p.ld_hr_mask % 4 == 0, "%s: hr_mask 16-byte rows", __func__);
-    for (int i = 0; i < 9; ++i) {
-        NERF_CHECK(p.wt_img[i] && (((uintptr_t)p.wt_img[i]) & 15u) == 0 && p.wt_img_rows[i] == b2::KPB[i],
-                   "%s: layer %d: weight-transpose chain image missing, unaligned or not %d rows", __func__, i,
-                   b2::KPB[i]);
-        NERF_CHECK(i == 0 || (p.in_mask[i] && p.ld_in_mask[i] >= 8 && (((uintptr_t)p.in_mask[i]) & 15u) == 0 &&
-                              p.ld_in_mask[i] % 4 == 0),
-                   "%s: layer %d: the input's ReLU words (ld >= 8, 16-byte rows) are required", __func__, i);
-    }
+    if (const int rc = chain_bwd_checked(__func__, p, true)) return rc;
     for (int i = 0; i < 10; ++i) {
         const int w = i == 0 ? 128 : 256;
         NERF_CHECK(p.dy[i] && p.lddy[i] == w && (((uintptr_t)p.dy[i]) & 15u) == 0 && p.dy_cmax[i] && p.dy_rmax[i],
@@ -2489,8 +2327,7 @@ extern "C" int nerf_mlp_chain_bwd(const nerf_chain_bwd* a, void* stream) {
 extern "C" int nerf_mlp_chain_bwd_rays(const nerf_chain_bwd* a, void* stream) {
     NERF_CHECK_PTR(a);
     const nerf_chain_bwd& p = *a;
-    NERF_CHECK(p.n_pad > 0 && p.n_pad % CROWS == 0, "%s: n_pad=%d must be a positive multiple of %d", __func__,
-               p.n_pad, CROWS);
+    if (const int rc = chain_bwd_checked(__func__, p, false)) return rc;
     // only D_0, D_5 and D_9 leave the kernel, with their row maxima and no column maxima: any
     // other pointer given here would stay unwritten
     for (int i = 0; i < 10; ++i) {
@@ -2503,19 +2340,6 @@ extern "C" int nerf_mlp_chain_bwd_rays(const nerf_chain_bwd* a, void* stream) {
             NERF_CHECK(!p.dy[i] && !p.dy_cmax[i] && !p.dy_rmax[i],
                        "%s: D_%d is not stored by the ray-gradient chain (dy, dy_cmax and dy_rmax must be NULL)",
                        __func__, i);
-    }
-    NERF_CHECK(gemm_precision() == 2, "%s: the chain runs in GEMM precision mode 2 (fp16 pair images)", __func__);
-    NERF_CHECK(p.graw4 && p.hr_mask && p.ld_hr_mask >= 4 && p.wd && p.wc,
-               "%s: graw4, the colour layer's ReLU words (ld >= 4), wd and wc are required", __func__);
-    NERF_CHECK_ALIGN16(p.graw4); NERF_CHECK_ALIGN16(p.wd);
-    NERF_CHECK((((uintptr_t)p.hr_mask) & 15u) == 0 && p.ld_hr_mask % 4 == 0, "%s: hr_mask 16-byte rows", __func__);
-    for (int i = 0; i < 9; ++i) {
-        NERF_CHECK(p.wt_img[i] && (((uintptr_t)p.wt_img[i]) & 15u) == 0 && p.wt_img_rows[i] == b2::KPB[i],
-                   "%s: layer %d: weight-transpose chain image missing, unaligned or not %d rows", __func__, i,
-                   b2::KPB[i]);
-        NERF_CHECK(i == 0 || (p.in_mask[i] && p.ld_in_mask[i] >= 8 && (((uintptr_t)p.in_mask[i]) & 15u) == 0 &&
-                              p.ld_in_mask[i] % 4 == 0),
-                   "%s: layer %d: the input's ReLU words (ld >= 8, 16-byte rows) are required", __func__, i);
     }
     ChainBwdArgs args{p};
     // the work of nerf_mlp_chain_bwd; HBM: graw4 and the ReLU words read, D_0, D_5, D_9 (f32) and
