@@ -32,14 +32,13 @@ def _pad_rows(n: int) -> int:
     return (n + _hip.ROW_TILE - 1) // _hip.ROW_TILE * _hip.ROW_TILE
 
 
-def _dw_splits(m: int, tiles: int, target_blocks: int = 512) -> int:
-    """Split-K factor for the weight-gradient GEMM: a power of two giving ~target blocks
-    with each split a whole number of 32-row K tiles."""
-    splits = 1
-    while (splits * 2 * tiles <= target_blocks and m % (splits * 2 * 32) == 0
-           and m // (splits * 2) >= 256):
-        splits *= 2
-    return splits
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _p10(tensors):
+    """The per-layer pointer array of the native backwards' argument structs (None: NULL)."""
+    return _hip._P10(*[_ptr(t) for t in tensors])
 
 
 @dataclass
@@ -324,14 +323,12 @@ class FieldRunner:
             return self.backward(st, g_rgb, g_dist, True, want_weight_grad=False)[1]
         Np, R, S = st["Np"], st["R"], st["S"]
         dev = st["z"].device
-        names = [l.name for l in self.layers]
-        P = lambda t: None if t is None else t.data_ptr()            # noqa: E731
+        P = _ptr
         ray = tuple(torch.empty(R, 3, device=dev) for _ in range(3))
         ws = torch.empty(_hip.field_bwd_rays_workspace_bytes(Np), device=dev, dtype=torch.uint8)
         args = _hip.FieldBwdRays(
-            Np, R, S, st["flags"], P(st["z"]), P(st["raw4"]), _hip._P10(*[P(st["masks"].get(n)) for n in names]),
-            P(st["pts_o"]), P(st["pts_d"]), P(st["view"]), _hip._P10(*[self.wt[n].data_ptr() for n in names]),
-            _hip._P10(*[self.wts[n].data_ptr() for n in names]), _hip._P10(*[self.wtsc[n].data_ptr() for n in names]),
+            Np, R, S, st["flags"], P(st["z"]), P(st["raw4"]), self._per_layer(st["masks"]),
+            P(st["pts_o"]), P(st["pts_d"]), P(st["view"]), *self._weight_ptrs(),
             self.wd.data_ptr(), self.wc.data_ptr(), P(g_rgb), P(g_dist), None, *[t.data_ptr() for t in ray],
             ws.data_ptr())
         _hip.field_backward_rays(args)
@@ -411,15 +408,22 @@ class FieldRunner:
         runs them as nine nerf_linear_bwd_data launches beside the weight gradients."""
         return os.environ.get("NERF_BWD_CHAIN", "1") != "0"
 
+    def _per_layer(self, by_name):
+        """A {layer name: tensor} dict as the structs' pointer array (a layer without one: NULL)."""
+        return _p10(by_name.get(l.name) for l in self.layers)
+
+    def _weight_ptrs(self):
+        """wt, wt_img, wt_cimg of nerf_field_bwd / nerf_field_bwd_rays: W^T, its fp16 pair image and its
+        chain image per layer."""
+        return tuple(_p10(d[l.name] for l in self.layers) for d in (self.wt, self.wts, self.wtsc))
+
     def _backward_native(self, st, g_rgb, g_dist, want_ray_grad, graw4, G):
         Np, R, S = st["Np"], st["R"], st["S"]
         dev = st["z"].device
         m = self.m
         if self._side is None or self._side[0].device != dev:
             self._side = [torch.cuda.Stream(dev)]
-        acts, masks, cms = st["acts"], st["masks"], st["cmaxes"]
-        names = [l.name for l in self.layers]
-        P = lambda t: None if t is None else t.data_ptr()            # noqa: E731
+        P = _ptr
         ray = None
         ray_ptrs = (None, None, None)
         if want_ray_grad:
@@ -430,13 +434,10 @@ class FieldRunner:
         args = _hip.FieldBwd(
             Np, R, S, st["flags"], int(want_ray_grad), int(os.environ.get("NERF_TAIL_MAIN", str(tail_default))),
             int(self.bwd_chain()), P(st["z"]), P(st["raw4"]), P(st["enc_p"]), P(st["enc_d"]), P(st["cmaxes"]["enc_p"]),
-            P(st["cmaxes"]["enc_d"]), _hip._P10(*[a.data_ptr() for a in acts]),
-            _hip._P10(*[P(masks.get(n)) for n in names]), _hip._P10(*[P(cms.get(n)) for n in names]),
-            P(st["pts_o"]), P(st["pts_d"]), P(st["view"]),
-            _hip._P10(*[self.wt[n].data_ptr() for n in names]), _hip._P10(*[self.wts[n].data_ptr() for n in names]),
-            _hip._P10(*[self.wtsc[n].data_ptr() for n in names]), self.wd.data_ptr(), self.wc.data_ptr(), P(g_rgb), P(g_dist), P(graw4),
-            _hip._P10(*[G(l.linear.weight).data_ptr() for l in self.layers]),
-            _hip._P10(*[G(l.linear.bias).data_ptr() for l in self.layers]),
+            P(st["cmaxes"]["enc_d"]), _p10(st["acts"]), self._per_layer(st["masks"]), self._per_layer(st["cmaxes"]),
+            P(st["pts_o"]), P(st["pts_d"]), P(st["view"]), *self._weight_ptrs(),
+            self.wd.data_ptr(), self.wc.data_ptr(), P(g_rgb), P(g_dist), P(graw4),
+            _p10(G(l.linear.weight) for l in self.layers), _p10(G(l.linear.bias) for l in self.layers),
             G(m.fc_density.weight).data_ptr(), G(m.fc_density.bias).data_ptr(), G(m.fc_rgb.weight).data_ptr(),
             G(m.fc_rgb.bias).data_ptr(), *ray_ptrs, ws.data_ptr())
         _hip.field_backward(args, self._side[0].cuda_stream)
@@ -524,26 +525,26 @@ class FieldRunner:
             if HR != D // 2:
                 G(m.fc_rgb.weight).copy_(gwc[:, :D // 2])
 
-        if not want_weight_grad:     # dyr alone (mode 1), gated by the ReLU words when the forward kept them
-            lr_mask = st["masks"].get("lr")
-            _hip.heads_bwd(graw4, None, h["lr"] if lr_mask is None else None, D, self.wc, dyr, None, Np,
-                           dyr_rmax=dy_rm, dyr_cmax=dy_cm, mode=1, hr_mask=lr_mask)
-        elif split_heads:
-            ev = torch.cuda.Event()
-            ev.record(main)
-            sides[0].wait_event(ev)
-            for t in (graw4, h["l7"], h["lr"]):
-                t.record_stream(sides[0])
-            with torch.cuda.stream(sides[0]):
-                head_weights(2)
-            lr_mask = st["masks"].get("lr")
-            _hip.heads_bwd(graw4, None, h["lr"] if lr_mask is None else None, D, self.wc, dyr, None, Np,
-                           dyr_rmax=dy_rm, dyr_cmax=dy_cm, mode=1, hr_mask=lr_mask)
-        else:
+        if want_weight_grad and not split_heads:
             head_weights(3)
+        else:
+            if want_weight_grad:
+                ev = torch.cuda.Event()
+                ev.record(main)
+                sides[0].wait_event(ev)
+                for t in (graw4, h["l7"], h["lr"]):
+                    t.record_stream(sides[0])
+                with torch.cuda.stream(sides[0]):
+                    head_weights(2)
+            # dyr alone (mode 1), gated by the ReLU words when the forward kept them
+            lr_mask = st["masks"].get("lr")
+            _hip.heads_bwd(graw4, None, h["lr"] if lr_mask is None else None, D, self.wc, dyr, None, Np,
+                           dyr_rmax=dy_rm, dyr_cmax=dy_cm, mode=1, hr_mask=lr_mask)
         fcm = st.get("cmaxes", {})
-        prev_cm = {"l0": "enc_p", "l1": "l0", "l2": "l1", "l3": "l2", "l4": "l3", "l5": "l4", "l6": "l5",
-                   "l7": "l6", "lf": "l7", "lr": "lf"}
+        # a layer's first input: the previous layer's output (l0: enc_p) -- the name its column maxima
+        # and ReLU words are kept under
+        prev = {l.name: self.layers[i - 1].name if i else "enc_p" for i, l in enumerate(self.layers)}
+        inputs = {**h, "enc_p": st["enc_p"]}
 
         # encoding gradients (pose learning): enc_p reaches layers l0 and l4 (skip), enc_d the
         # colour layer; each GEMM writes its own buffer and encode_bwd sums the two enc_p ones
@@ -560,11 +561,7 @@ class FieldRunner:
         tail_default = 2 if (D == 256 and Np >= 65536) else 0
         tail_main = int(os.environ.get("NERF_TAIL_MAIN", str(tail_default)))
         dy = dyr
-        prev_in = {"l0": st["enc_p"], "l1": h["l0"], "l2": h["l1"], "l3": h["l2"], "l4": h["l3"],
-                   "l5": h["l4"], "l6": h["l5"], "l7": h["l6"], "lf": h["l7"], "lr": h["lf"]}
         order = ["lr", "lf", "l7", "l6", "l5", "l4", "l3", "l2", "l1", "l0"]
-        prev_name = {"l1": "l0", "l2": "l1", "l3": "l2", "l4": "l3", "l5": "l4", "l6": "l5", "l7": "l6",
-                     "lf": "l7", "lr": "lf"}
         spec = {l.name: l for l in self.layers}
         seg_buf = {"enc_p": st["enc_p"], "enc_d": st["enc_d"]}
         def weight_grad(l, dy, dy_cm, x_in):
@@ -580,10 +577,10 @@ class FieldRunner:
                 # both input segments in one launch (dy read once; nerf_linear_bwd_weight_seg).
                 # NERF_DW_SEG=0 (A/B only): the two launches of round 3's first half
                 _hip.linear_bwd_weight_seg(dy, l.out_p, x_in, k1, seg_buf[l.seg2], 64, Np, splits, slab, l.kp, bslab,
-                                           dy_cmax=dy_cm, x1_cmax=fcm.get(prev_cm[l.name]), x2_cmax=fcm.get(l.seg2))
+                                           dy_cmax=dy_cm, x1_cmax=fcm.get(prev[l.name]), x2_cmax=fcm.get(l.seg2))
             else:
                 _hip.linear_bwd_weight(dy, l.out_p, x_in, k1, Np, splits, slab, l.kp, 0, bslab, dy_cmax=dy_cm,
-                                       x_cmax=fcm.get(prev_cm[l.name]))
+                                       x_cmax=fcm.get(prev[l.name]))
                 if l.seg2:
                     _hip.linear_bwd_weight(dy, l.out_p, seg_buf[l.seg2], 64, Np, splits, slab, l.kp, k1, None,
                                            dy_cmax=dy_cm, x_cmax=fcm.get(l.seg2))
@@ -596,7 +593,7 @@ class FieldRunner:
         for step, name in enumerate(order):
             l = spec[name]
             W = l.linear.weight
-            x_in = prev_in[name]
+            x_in = inputs[prev[name]]
             k1 = l.k1
             # --- weight / bias gradient on a side stream: split-K slabs + reduce.  The last
             # NERF_TAIL_MAIN layers' run on the main stream once the input-gradient chain is done
@@ -632,7 +629,7 @@ class FieldRunner:
             dx = e(Np, k1)
             dx_rm, dx_cm = rm(k1), cm(k1)
             # ReLU bits of this layer's input (f, the input of lr, has no activation)
-            mask = None if name == "lr" else st["masks"][prev_name[name]]
+            mask = None if name == "lr" else st["masks"][prev[name]]
             if name == "lf":   # + density path: d sigma_raw (graw4[:,0]) x w_density
                 _hip.linear_bwd_data(dy, l.out_p, wt[:k1], dx, Np, k1, mask=mask, u=graw4, ldu=4,
                                      v=self.wd.view(-1), wt_split=rows(0, k1), dy_rmax=dy_rm, dx_rmax=dx_rm,

@@ -1,5 +1,5 @@
 """Probe: are the cfg2 train step's results independent of the head-reduce placement
-(NERF_HEADS_PLACE 5, the default, forks k_heads_reduce to the side stream; 1 keeps it on the
+(NERF_HEADS_PLACE 5 forks k_heads_reduce to the side stream; 1, the default, keeps it on the
 caller's stream)?  The placement moves no arithmetic, so with the same seeds the two must give
 bit-identical losses step after step; a difference points at a missing stream dependency.  Each
 placement trains one trainer eagerly and one as replays of a captured step (bench.measure_graph's
