@@ -45,7 +45,7 @@ extern "C" {
  * 15 the chain images' compact exponent arrays (nerf_pack_desc dst_cs / dst_cts) and
  * nerf_linear_bwd_weight_job_groups.  Additive within 15 (no existing signature changed): the
  * frozen-field entries, nerf_image_metrics(_workspace_bytes) and nerf_pair_forward_ssim /
- * nerf_pair_backward_ssim, nerf_pair_backward_cam. */
+ * nerf_pair_backward_ssim, nerf_pair_backward_cam, nerf_depth_metrics(_workspace_bytes). */
 #define NERF_HIP_ABI_VERSION 15
 int nerf_hip_abi_version(void);
 const char* nerf_hip_last_error(void);
@@ -939,6 +939,37 @@ int nerf_image_metrics(const float* img1, int64_t s1_batch, int64_t s1_channel, 
                        const float* img2, int64_t s2_batch, int64_t s2_channel, int64_t s2_row, int64_t s2_col,
                        int batch, int channels, int height, int width, int window, int use_padding, float* out,
                        float* ssim_map, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Depth metrics of the novel-view evaluation (metrics.hip; model/eval_images.py:105-107, 152-160,
+ * 200-201 and compute_errors, model/common.py:676-694).  Per image b of the batch, for every pixel
+ * (Y, X) of the H x W ground-truth grid:
+ *   d  = fl32(pred[iy][ix] * sc), iy = min(((2 Y + 1) h) / (2 H), h - 1), ix likewise (integers): the
+ *        pixel-centre nearest neighbour of cv2.INTER_NEAREST_EXACT after numpy's in-place f32 scaling;
+ *   g  = gt[Y][X];  mr = d >= min_depth && d <= max_depth, mg the same on g (f32 comparisons, both
+ *        bounds inclusive; NaN, +-inf, 0 and negative values are out of range);
+ *   tp = mr & mg, fn = !mr & mg, fp = mr & !mg, tn = !mr & !mg, counted exactly;
+ *   over the tp pixels, in fp64 from the f32 values: |g - d| / g, (g - d)^2 / g, (g - d)^2,
+ *   (log g - log d)^2 and the indicators max(g / d, d / g) < 1.25, 1.5625, 1.953125.
+ *   out[b] = { abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, tp, fn, fp, tn } as doubles: means over
+ *   the tp pixels, the two rmse values the square roots of means.  With tp == 0 the seven errors
+ *   are NaN (numpy's mean of an empty selection) and the counts still hold.
+ * pred ([batch][h][w]) and gt ([batch][H][W]) are addressed by three element strides (batch, row,
+ * column) and read in place; no resized copy is made.  depth_out (optional): contiguous
+ * [batch][H][W], the resampled, scaled d.  mask_out (optional): contiguous [batch][H][W] bytes,
+ * bit 0 = mr, bit 1 = mg (the three mask images of eval_images.py:194-196 derive from them).
+ * workspace: nerf_depth_metrics_workspace_bytes bytes, 8-byte aligned (eleven partial sums per
+ * 1024 pixels, summed in a fixed order: no atomics, repeatable bits, a batch returns what its
+ * single-image calls return).  Two launches, no host synchronisation.
+ * Refused before any HIP call (NERF_EINVAL): a null pred, gt, out or workspace; h, w, H, W or
+ * batch < 1; H * W >= 2^31; a non-finite sc; min_depth <= 0, max_depth < min_depth or a NaN bound
+ * (log and the ratios are undefined at 0; the reference never checks).
+ * nerf_depth_metrics_workspace_bytes returns 0 for a non-positive argument. */
+size_t nerf_depth_metrics_workspace_bytes(int batch, int gt_height, int gt_width);
+int nerf_depth_metrics(const float* pred, int64_t sp_batch, int64_t sp_row, int64_t sp_col, int h, int w,
+                       const float* gt, int64_t sg_batch, int64_t sg_row, int64_t sg_col, int H, int W,
+                       int batch, float sc, float min_depth, float max_depth, double* out, float* depth_out,
+                       uint8_t* mask_out, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Timing hooks for bench.py: when enabled, every GEMM launch is bracketed by

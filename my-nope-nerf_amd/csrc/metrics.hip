@@ -22,6 +22,9 @@
 // window 3.  So the 2-D window is applied as it is: each thread owns four vertically adjacent
 // outputs and walks the window rows once, so a staged pixel is read once per four outputs; 5 x 121
 // fp64 FMAs per output.
+//
+// The depth half of the same evaluation (k_depth_metrics, k_depth_metrics_final) follows the image
+// metrics below.
 #include "common.hpp"
 
 #include <cmath>
@@ -162,6 +165,119 @@ __global__ __launch_bounds__(kWave) void k_image_metrics_final(const double* __r
 
 static inline int metric_tiles(int n) { return (n + MT - 1) / MT; }
 
+// ---- depth metrics (model/eval_images.py:105-107, 152-160, 200-201 and model/common.py:676-694 of the
+// reference): the rendered depth is resampled to the ground truth's grid by pixel-centre nearest
+// neighbour and scaled inside the kernel, both range masks, the four confusion counts and the seven
+// error sums over the pixels in range in both come from one pass.
+//   k_depth_metrics       : one workgroup per (DPIX consecutive pixels of the gt grid, image); thread t
+//                           takes pixels t, t + 256, ... of the block's span, so a wavefront reads 64
+//                           consecutive gt pixels.  Eleven doubles per block go to the workspace;
+//   k_depth_metrics_final : one wavefront per image sums them in a fixed order and finishes the means.
+// The selection is made on the f32 values exactly as numpy makes it; everything after is fp64 (the
+// counts too: integers below 2^31 sum exactly).  No atomics.
+constexpr int DTHREADS = 256;
+constexpr int DPPT = 4;                 // pixels per thread
+constexpr int DPIX = DTHREADS * DPPT;   // pixels per workgroup
+constexpr int DN = 11;                  // four error sums, three indicator counts, tp, fn, fp, tn
+
+struct DepthArgs {
+    const float* pred; const float* gt;
+    long long sp[3], sg[3];             // element strides: batch, row, column
+    int h, w, H, W;
+    float sc, lo, hi;
+    double* part;                       // [B][blocks][DN]
+    float* depth;                       // [B][H][W] or NULL
+    unsigned char* mask;                // [B][H][W] or NULL
+};
+
+__global__ __launch_bounds__(DTHREADS) void k_depth_metrics(DepthArgs p) {
+    __shared__ double red[DN][DTHREADS / kWave];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const long long n_pix = (long long)p.H * p.W;        // < 2^31 (checked by the entry)
+    const float* pp = p.pred + b * p.sp[0];
+    const float* pg = p.gt + b * p.sg[0];
+
+    double v[DN];
+#pragma unroll
+    for (int k = 0; k < DN; ++k) v[k] = 0.;
+#pragma unroll
+    for (int k = 0; k < DPPT; ++k) {
+        const long long i = (long long)blockIdx.x * DPIX + k * DTHREADS + tid;
+        if (i >= n_pix) continue;
+        const int Y = (int)(i / p.W), X = (int)(i - (long long)Y * p.W);
+        // pixel-centre nearest neighbour (cv2.INTER_NEAREST_EXACT): (2 Y + 1) h < 2^63
+        const long long iy = min(((2LL * Y + 1) * p.h) / (2LL * p.H), (long long)p.h - 1);
+        const long long ix = min(((2LL * X + 1) * p.w) / (2LL * p.W), (long long)p.w - 1);
+        const float d = pp[iy * p.sp[1] + ix * p.sp[2]] * p.sc;           // one f32 multiply (depth_out *= sc)
+        const float g = pg[Y * p.sg[1] + X * p.sg[2]];
+        const bool mr = d >= p.lo && d <= p.hi, mg = g >= p.lo && g <= p.hi;   // NaN, inf, 0, negatives: false
+        if (p.depth) p.depth[(size_t)b * n_pix + i] = d;
+        if (p.mask) p.mask[(size_t)b * n_pix + i] = (unsigned char)((mr ? 1 : 0) | (mg ? 2 : 0));
+        if (mr && mg) {
+            const double gd = (double)g, dd = (double)d, diff = gd - dd, sq = diff * diff;
+            const double lg = log(gd) - log(dd);
+            const double r = fmax(gd / dd, dd / gd);
+            v[0] += fabs(diff) / gd;
+            v[1] += sq / gd;
+            v[2] += sq;
+            v[3] += lg * lg;
+            v[4] += r < 1.25 ? 1. : 0.;
+            v[5] += r < 1.5625 ? 1. : 0.;
+            v[6] += r < 1.953125 ? 1. : 0.;
+            v[7] += 1.;
+        } else if (mg) {
+            v[8] += 1.;                 // fn: gt in range, rendered not
+        } else if (mr) {
+            v[9] += 1.;                 // fp
+        } else {
+            v[10] += 1.;                // tn
+        }
+    }
+
+    // wavefront, then the four wavefronts in order
+#pragma unroll
+    for (int k = 0; k < DN; ++k) {
+        v[k] = wave_sum_f64(v[k]);
+        if (lane_id() == 0) red[k][tid / kWave] = v[k];
+    }
+    __syncthreads();
+    if (tid < DN)
+        p.part[((size_t)b * gridDim.x + blockIdx.x) * DN + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+}
+
+// out[b] = {abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, tp, fn, fp, tn} of image b: its n partials, lane l
+// taking l, l + 64, ... in order; tp == 0 leaves the seven errors 0 / 0 = NaN, as numpy's mean of nothing is
+__global__ __launch_bounds__(kWave) void k_depth_metrics_final(const double* __restrict__ part, int n,
+                                                              double* __restrict__ out) {
+    const double* q = part + (size_t)blockIdx.x * n * DN;
+    double v[DN];
+#pragma unroll
+    for (int k = 0; k < DN; ++k) v[k] = 0.;
+    for (int i = threadIdx.x; i < n; i += kWave) {
+#pragma unroll
+        for (int k = 0; k < DN; ++k) v[k] += q[(size_t)i * DN + k];
+    }
+#pragma unroll
+    for (int k = 0; k < DN; ++k) v[k] = wave_sum_f64(v[k]);
+    if (threadIdx.x == 0) {
+        double* o = out + (size_t)blockIdx.x * DN;
+        const double tp = v[7];
+        o[0] = v[0] / tp;
+        o[1] = v[1] / tp;
+        o[2] = sqrt(v[2] / tp);
+        o[3] = sqrt(v[3] / tp);
+        o[4] = v[4] / tp;
+        o[5] = v[5] / tp;
+        o[6] = v[6] / tp;
+        o[7] = tp;
+        o[8] = v[8];
+        o[9] = v[9];
+        o[10] = v[10];
+    }
+}
+
+static inline long long depth_blocks(int H, int W) { return ((long long)H * W + DPIX - 1) / DPIX; }
+
 }  // namespace nerf
 
 using namespace nerf;
@@ -227,5 +343,48 @@ extern "C" int nerf_image_metrics(const float* img1, int64_t s1_batch, int64_t s
     }
     hipLaunchKernelGGL(k_image_metrics_final, dim3(batch), dim3(kWave), 0, s, (const double*)p.part, channels * ty * tx,
                        (double)channels * height * width, (double)channels * p.Ho * p.Wo, out);
+    return check_launch(__func__);
+}
+
+extern "C" size_t nerf_depth_metrics_workspace_bytes(int batch, int gt_height, int gt_width) {
+    if (batch <= 0 || gt_height <= 0 || gt_width <= 0) return 0;
+    return (size_t)batch * (size_t)depth_blocks(gt_height, gt_width) * DN * sizeof(double);
+}
+
+extern "C" int nerf_depth_metrics(const float* pred, int64_t sp_batch, int64_t sp_row, int64_t sp_col, int h, int w,
+                                  const float* gt, int64_t sg_batch, int64_t sg_row, int64_t sg_col, int H, int W,
+                                  int batch, float sc, float min_depth, float max_depth, double* out, float* depth_out,
+                                  uint8_t* mask_out, void* workspace, void* stream) {
+    NERF_CHECK_PTR(pred); NERF_CHECK_PTR(gt); NERF_CHECK_PTR(out);
+    NERF_CHECK(workspace != nullptr, "%s: null pointer 'workspace' (nerf_depth_metrics_workspace_bytes)", __func__);
+    NERF_CHECK((((uintptr_t)workspace) & 7u) == 0, "%s: pointer 'workspace' not 8-byte aligned", __func__);
+    NERF_CHECK((((uintptr_t)out) & 7u) == 0, "%s: pointer 'out' not 8-byte aligned", __func__);
+    NERF_CHECK(h > 0, "%s: h=%d", __func__, h);
+    NERF_CHECK(w > 0, "%s: w=%d", __func__, w);
+    NERF_CHECK(H > 0, "%s: H=%d", __func__, H);
+    NERF_CHECK(W > 0, "%s: W=%d", __func__, W);
+    NERF_CHECK(batch > 0, "%s: batch=%d", __func__, batch);
+    NERF_CHECK(batch <= 65535, "%s: batch=%d exceeds the grid's 65535", __func__, batch);
+    NERF_CHECK((long long)H * W < (1LL << 31), "%s: H * W = %lld must be below 2^31", __func__, (long long)H * W);
+    NERF_CHECK(std::isfinite(sc), "%s: sc=%g must be finite", __func__, (double)sc);
+    // log and the ratios are undefined at 0: the reference never checks, this entry says so
+    NERF_CHECK(min_depth > 0.f, "%s: min_depth=%g must be positive", __func__, (double)min_depth);
+    NERF_CHECK(max_depth >= min_depth, "%s: max_depth=%g must be at least min_depth=%g", __func__, (double)max_depth,
+               (double)min_depth);
+
+    DepthArgs p;
+    p.pred = pred; p.gt = gt;
+    p.sp[0] = sp_batch; p.sp[1] = sp_row; p.sp[2] = sp_col;
+    p.sg[0] = sg_batch; p.sg[1] = sg_row; p.sg[2] = sg_col;
+    p.h = h; p.w = w; p.H = H; p.W = W;
+    p.sc = sc; p.lo = min_depth; p.hi = max_depth;
+    p.part = static_cast<double*>(workspace);
+    p.depth = depth_out;
+    p.mask = mask_out;
+
+    const int blocks = (int)depth_blocks(H, W);          // < 2^21
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(k_depth_metrics, dim3(blocks, batch), dim3(DTHREADS), 0, s, p);
+    hipLaunchKernelGGL(k_depth_metrics_final, dim3(batch), dim3(kWave), 0, s, (const double*)p.part, blocks, out);
     return check_launch(__func__);
 }

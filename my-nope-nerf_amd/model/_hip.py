@@ -208,6 +208,9 @@ _SIGS = {
     "nerf_image_metrics_workspace_bytes": ([_c_i, _c_i, _c_i, _c_i], ctypes.c_size_t),
     "nerf_image_metrics": ([_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i, _c_i,
                             _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p], _c_i),
+    "nerf_depth_metrics_workspace_bytes": ([_c_i, _c_i, _c_i], ctypes.c_size_t),
+    "nerf_depth_metrics": ([_c_p, _c_i64, _c_i64, _c_i64, _c_i, _c_i, _c_p, _c_i64, _c_i64, _c_i64, _c_i, _c_i,
+                            _c_i, _c_f, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p], _c_i),
     "nerf_prof_enable": ([_c_i], _c_i),
     "nerf_prof_read_kinds": ([ctypes.POINTER(ProfKind), _c_i], _c_i),
     "nerf_prof_read": ([ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64),
@@ -803,6 +806,38 @@ def image_metrics(img1, img2, window, use_padding, out, work, ssim_map=None):
     b, c, h, w = img1.shape
     _call("nerf_image_metrics", _ptr(img1), *img1.stride(), _ptr(img2), *img2.stride(), b, c, h, w, int(window),
           int(bool(use_padding)), _ptr(out), _ptr(ssim_map), _ptr(work), _stream())
+
+
+def depth_metrics_workspace_bytes(batch, height, width) -> int:
+    return int(lib().nerf_depth_metrics_workspace_bytes(int(batch), int(height), int(width)))
+
+
+def depth_metrics(pred, gt, sc, min_depth, max_depth, out, work, depth_out=None, mask_out=None):
+    """out [B][11] float64 = (abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, tp, fn, fp, tn) of float32
+    views pred [B,h,w] and gt [B,H,W] of any strides, read in place (nerf_depth_metrics): pred is
+    resampled to gt's grid by pixel-centre nearest neighbour and scaled by sc inside the kernel.
+    work: depth_metrics_workspace_bytes(B, H, W) bytes; depth_out: optional contiguous float32
+    [B][H][W], the resampled scaled depth; mask_out: optional contiguous uint8 [B][H][W], bit 0 the
+    rendered depth in [min_depth, max_depth], bit 1 the ground truth."""
+    if pred.dim() != 3 or gt.dim() != 3 or pred.shape[0] != gt.shape[0]:
+        raise ValueError(f"depth_metrics: [B,h,w] and [B,H,W] tensors of one batch expected, got {tuple(pred.shape)} "
+                         f"and {tuple(gt.shape)}")
+    for t in (pred, gt, out, depth_out, mask_out):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("nerf_hip: tensor must live on the GPU (no CPU fallback)")
+    for t in (pred, gt, depth_out):
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError("depth_metrics: float32 depths expected")
+    if out.dtype != torch.float64 or (mask_out is not None and mask_out.dtype != torch.uint8):
+        raise RuntimeError("depth_metrics: a float64 out and a uint8 mask_out expected")
+    b, h, w = pred.shape
+    _, gh, gw = gt.shape
+    if tuple(out.shape) != (b, 11) or any(t is not None and tuple(t.shape) != (b, gh, gw) for t in (depth_out, mask_out)):
+        raise ValueError("depth_metrics: out must be [B,11], depth_out and mask_out [B,H,W]")
+    if not all(t is None or t.is_contiguous() for t in (out, depth_out, mask_out)):
+        raise RuntimeError("depth_metrics: contiguous outputs expected")
+    _call("nerf_depth_metrics", _ptr(pred), *pred.stride(), h, w, _ptr(gt), *gt.stride(), gh, gw, b, float(sc),
+          float(min_depth), float(max_depth), out.data_ptr(), _ptr(depth_out), _ptr(mask_out), _ptr(work), _stream())
 
 
 def chamfer_nn(x, y, idx):

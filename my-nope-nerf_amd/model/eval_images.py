@@ -10,6 +10,11 @@ device-to-host copy of the two scalars per frame (the reference: three .item() c
 convolutions and two permuted copies).  Everything after the metrics is host numpy, as in the
 reference.
 
+Additions: ``eval_metrics`` returns the image metrics and the depth metrics (one nerf_depth_metrics
+call: resample, masks, confusion counts and compute_errors' seven errors in fp64) of a frame as
+device tensors, writing nothing; ``summarise`` turns a list of them into the table of
+evaluation/eval.py:190-212 with one device-to-host copy.
+
 Deviations: ``lpips_vgg_fn=None`` gives ``float('nan')`` for 'lpips' (the lpips package is a VGG
 network and stays the caller's to provide; the reference would raise).  Images are written with
 PIL, the disparity colour map is matplotlib's inferno and the depth resize is
@@ -24,7 +29,7 @@ import torch
 
 from .common import mse2psnr
 from .extracting_images import Extract_Images, _inferno, _to_u8_range, _write_png
-from .metrics import image_metrics, resize_nearest_exact
+from .metrics import DEPTH_METRIC_NAMES, depth_metrics, image_metrics, resize_nearest_exact
 
 
 class Eval_Images(object):
@@ -55,6 +60,54 @@ class Eval_Images(object):
         scale_mat = data.get("img.scale_mat").to(device)
         return (img, depth_img, camera_mat, scale_mat, img_idx, depth_gt)
 
+    def _frame_cameras(self, img_idx, camera_mat, fxfy):
+        """(camera_mat, world_mat) of a held-out frame (eval_images.py:59-66): the learnt pose's
+        inverse and the learnt focal's camera matrix where the evaluator uses them."""
+        world_mat = None
+        if self.use_learnt_poses:
+            world_mat = torch.inverse(self.c2ws[img_idx]).unsqueeze(0)
+        if self.use_learnt_focal:
+            camera_mat = torch.tensor([[[fxfy[0], 0, 0, 0], [0, -fxfy[1], 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]]],
+                                      dtype=torch.float32, device=self.device)
+        return camera_mat, world_mat
+
+    def eval_metrics(self, data, fxfy, min_depth=0.1, max_depth=20, it=0, sc=1):
+        """The numbers of eval_images without its files: the same pose / focal handling and the same
+        render_frame, then one image_metrics call and one depth_metrics call.  The ground-truth depth
+        (img.gt_depths, or img.depth when absent, :53-57) is uploaded once as float32.  Returns
+        {"image": [2] float32 (mse, ssim), "depth": [11] float64 (metrics.DEPTH_METRIC_NAMES)} as
+        tensors on the renderer's device: no file is written and nothing is copied to the host, so the
+        frames of a sequence can be stacked and read back once (summarise)."""
+        self.renderer.eval()
+        (img_gt, depth, camera_mat, scale_mat, img_idx, depth_gt) = self.process_data_dict(data)
+        img_idx = int(img_idx)
+        if depth_gt is None:
+            depth_gt = depth
+        camera_mat, world_mat = self._frame_cameras(img_idx, camera_mat, fxfy)
+        with torch.no_grad():
+            img_out, depth_pred = self.render_frame(camera_mat, world_mat, scale_mat, it)
+            depth_gt = depth_gt.squeeze(0).to(device=depth_pred.device, dtype=torch.float32)
+            return {"image": image_metrics(img_out, img_gt),
+                    "depth": depth_metrics(depth_pred, depth_gt, min_depth, max_depth, sc=sc)}
+
+    @staticmethod
+    def summarise(records):
+        """The table of evaluation/eval.py:190-212 from a list of eval_metrics results, with one
+        device-to-host copy: the means over the frames of mse, psnr (of each frame's mse) and ssim, of
+        the seven depth errors, and of the confusion matrix [[tp, fn], [fp, tn]] divided per frame by
+        H*W - 1 -- the reference divides by the last pixel INDEX, not the pixel count
+        (eval_images.py:162, 217); kept, so the table matches the reference's."""
+        if not records:
+            raise ValueError("summarise: no records")
+        table = torch.stack([torch.cat([r["image"].double(), r["depth"]]) for r in records]).cpu().numpy()
+        image, errors, counts = table[:, :2], table[:, 2:9], table[:, 9:13]
+        conf = (counts / (counts.sum(1, keepdims=True) - 1)).mean(0)
+        out = {"mse": float(image[:, 0].mean()), "psnr": float(np.mean([mse2psnr(m) for m in image[:, 0]])),
+               "ssim": float(image[:, 1].mean())}
+        out.update({k: float(v) for k, v in zip(DEPTH_METRIC_NAMES[:7], errors.mean(0))})
+        out["conf_mat"] = conf.reshape(2, 2)
+        return out
+
     def eval_images(self, data, render_dir, fxfy, lpips_vgg_fn, logger, min_depth=0.1, max_depth=20, it=0, sc=1,
                     show_errors=False):
         """eval_images.py:47-218."""
@@ -68,12 +121,7 @@ class Eval_Images(object):
             print("No GT depths available, using input depths")
             depth_gt = depth.squeeze(0).numpy()
 
-        world_mat = None
-        if self.use_learnt_poses:
-            world_mat = torch.inverse(self.c2ws[img_idx]).unsqueeze(0)
-        if self.use_learnt_focal:
-            camera_mat = torch.tensor([[[fxfy[0], 0, 0, 0], [0, -fxfy[1], 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]]],
-                                      dtype=torch.float32, device=self.device)
+        camera_mat, world_mat = self._frame_cameras(img_idx, camera_mat, fxfy)
 
         with torch.no_grad():
             img_out, depth_pred = self.render_frame(camera_mat, world_mat, scale_mat, it)

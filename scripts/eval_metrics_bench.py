@@ -12,7 +12,14 @@ one pair of hipEvents; the variants are interleaved over `--rounds` rounds and t
 per-call times go to a JSON file, with the kernel launches per call counted by torch.profiler.
 Not part of the suite or of bench.py.
 
+With --depth the same scheme measures the depth half instead, a 188 x 621 rendered depth against a
+375 x 1242 ground truth, both on the device: model.metrics.depth_metrics (one nerf_depth_metrics
+call), the same with the two planes, and the host path Eval_Images.eval_images runs (.cpu(),
+resize_nearest_exact, the masks, the counts, compute_errors), timed by the wall clock because its
+copy synchronises.
+
     python scripts/eval_metrics_bench.py [--calls 100 --rounds 7 --out profiles/eval_metrics/bench.json]
+    python scripts/eval_metrics_bench.py --depth [--out profiles/eval_metrics/depth_bench.json]
 """
 from __future__ import annotations
 
@@ -82,15 +89,102 @@ def torch_metrics(hwc, gt, window=None):
     return mse, m.mean()
 
 
+def depth_pair(h, w, gh, gw, seed=0):
+    """(pred [h,w], gt [gh,gw]) on the CPU: depths 0.05 + 30 U^2, a share outside [0.1, 20], and a
+    noisy bilinear copy at the render's resolution."""
+    g = torch.Generator().manual_seed(seed)
+    gt = (0.05 + 30.0 * torch.rand(gh, gw, generator=g) ** 2).float()
+    pred = F.interpolate(gt[None, None], size=(h, w), mode="bilinear", align_corners=False)[0, 0]
+    return (pred * torch.exp(0.25 * torch.randn(h, w, generator=g))).float().contiguous(), gt.contiguous()
+
+
+def host_depth_metrics(depth_pred, depth_gt, sc, lo, hi):
+    """What Eval_Images.eval_images and evaluation/eval.py:200-209 do for the depth of one frame: the
+    rendered depth copied to the host, scaled, resized, both masks, the four counts and
+    compute_errors in float32 (the ground truth is on the host already, as the loader leaves it)."""
+    import numpy as np
+    from model.common import compute_errors
+    from model.metrics import resize_nearest_exact
+    d = depth_pred.cpu().numpy().copy()
+    d *= sc
+    d = resize_nearest_exact(d, depth_gt.shape)
+    mr, mg = (d >= lo) & (d <= hi), (depth_gt >= lo) & (depth_gt <= hi)
+    m = mr & mg
+    counts = [np.sum(m), np.sum(~mr & mg), np.sum(mr & ~mg), np.sum(~mr & ~mg)]
+    return [float(v) for v in compute_errors(depth_gt[m], d[m])] + [float(c) for c in counts]
+
+
+def depth_main(args):
+    """--depth: (a) metrics.depth_metrics, (b) the same with the planes, (c) the host path, for a
+    188 x 621 rendered depth against a 375 x 1242 ground truth, both on the device."""
+    import time
+    from model import _hip, metrics
+    _hip.load_library()
+    dev = torch.device("cuda", 0)
+    gh, gw, sc, lo, hi = 375, 1242, 1.7, 0.1, 20.0
+    pred_cpu, gt_cpu = depth_pair(H, W, gh, gw)
+    pred, gt, gt_np = pred_cpu.to(dev), gt_cpu.to(dev), gt_cpu.numpy()
+    device_variants = {"hip_depth_metrics": lambda: metrics.depth_metrics(pred, gt, lo, hi, sc=sc),
+                       "hip_depth_metrics_planes": lambda: metrics.depth_metrics(pred, gt, lo, hi, sc=sc, planes=True)}
+    got = metrics.depth_metrics(pred, gt, lo, hi, sc=sc).tolist()
+    host = host_depth_metrics(pred, gt_np, sc, lo, hi)
+    if got[7:] != host[7:] or max(abs(a - b) for a, b in zip(got[:7], host[:7])) > 1e-3:
+        raise RuntimeError(f"depth metrics disagree: hip {got}, host {host}")
+    for fn in device_variants.values():
+        for _ in range(args.warmup):
+            fn()
+    for _ in range(3):
+        host_depth_metrics(pred, gt_np, sc, lo, hi)
+    torch.cuda.synchronize()
+    times = {k: [] for k in list(device_variants) + ["host_numpy_f32"]}
+    host_calls = max(1, args.calls // 20)              # milliseconds each: fewer calls per round
+    for _ in range(args.rounds):
+        for name, fn in device_variants.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(args.calls):
+                fn()
+            b.record()
+            b.synchronize()
+            times[name].append(1e3 * a.elapsed_time(b) / args.calls)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(host_calls):
+            host_depth_metrics(pred, gt_np, sc, lo, hi)      # its .cpu() waits for the device: wall clock
+        times["host_numpy_f32"].append(1e6 * (time.perf_counter() - t0) / host_calls)
+    res = {"shape": {"height": H, "width": W, "gt_height": gh, "gt_width": gw, "sc": sc, "min_depth": lo,
+                     "max_depth": hi},
+           "method": f"{args.rounds} interleaved rounds; device variants: {args.calls} warm calls between one hipEvent "
+                     f"pair, no result read back; host path: {host_calls} calls by the wall clock, its device-to-host "
+                     "copy included; us per call",
+           "values": {"hip": dict(zip(metrics.DEPTH_METRIC_NAMES, got)),
+                      "host_numpy_f32": dict(zip(metrics.DEPTH_METRIC_NAMES, host))}}
+    for name, v in times.items():
+        res[name] = {"median_us": statistics.median(v), "min_us": min(v), "max_us": max(v), "rounds": len(v),
+                     "launches_per_call": None}
+    for name, fn in device_variants.items():
+        res[name]["launches_per_call"] = launches(fn)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=100)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_metrics", "bench.json"))
+    ap.add_argument("--depth", action="store_true", help="measure the depth metrics instead (depth_bench.json)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.calls < 100:
         raise SystemExit("--calls: at least 100 warm calls per round")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "eval_metrics", "depth_bench.json" if args.depth else "bench.json")
+    if args.depth:
+        return depth_main(args)
     from model import _hip, metrics
     _hip.load_library()
     dev = torch.device("cuda", 0)
