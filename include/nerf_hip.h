@@ -400,8 +400,9 @@ int nerf_mlp_chain_frozen(const float* enc_p, const float* enc_d, const float* e
  * pts_o / pts_d / view: [R][3] ray origins, sample directions, view directions; layers: the
  * ten chain descriptors with out / mask / cmax NULL; wd [256], bd [1]: fc_density; wc [3][128]
  * (padded), bc [3]: fc_rgb.  flags as nerf_composite_fwd.  Outputs rgb [R][3], dist [R]
- * (ray distance; the caller applies the eval z-depth division), alpha [R][S], z [R*S].
- * GEMM precision mode 2, hidden width 256.  Replaces rendering.py:89-141 +
+ * (ray distance; the caller applies the eval z-depth division), alpha [R][S], z [R*S]; the
+ * four outputs 16-byte aligned as every pointer here (checked: alpha is stored as float4 for
+ * S >= 64).  GEMM precision mode 2, hidden width 256.  Replaces rendering.py:89-141 +
  * official_nerf.py:60-96 for the render callers (extracting_images.py:65-76,
  * training.py:103-165). */
 int nerf_render_eval_fused(const float* pts_o, const float* pts_d, const float* view, int n_rays, int n_samples,

@@ -1498,7 +1498,8 @@ __device__ __forceinline__ void fused_encode_d_rows(const ChainFwdArgs& p, float
 
 // eval epilogue: sigma -> alpha -> exclusive-product compositing of the block's 128 / S rays
 // (rendering.py:113-141), from the raw4 / z rows in LDS, with the arithmetic of
-// k_composite16_fwd (so the fused and the unfused render agree bit for bit): one 16-lane DPP
+// k_composite16_fwd (so the fused and the staged render agree bit for bit: held by
+// tests/test_gpu_fused_eval_fp64.py::test_bit_identical_to_the_staged_path): one 16-lane DPP
 // row per ray, lane l owning samples [l J, l J + J) (J = max(1, S / 16)); transmittance by a
 // row prefix-product scan, the sums by row butterflies; each lane stores its J alphas as
 // contiguous float4s (a ray's S alphas are one contiguous run across its row)
@@ -2280,6 +2281,8 @@ extern "C" int nerf_render_eval_fused(const float* pts_o, const float* pts_d, co
     NERF_CHECK((int64_t)n_rays * n_samples <= (int64_t)1 << 30, "%s: too many samples", __func__);
     NERF_CHECK(gemm_precision() == 2, "%s: the fused chain runs in GEMM precision mode 2 (fp16 pair images)", __func__);
     NERF_CHECK((flags & ~7) == 0, "%s: unknown flags %d", __func__, flags);
+    // the header's pointer contract: alpha is stored as float4 for S >= 64 (fused_composite16)
+    NERF_CHECK_ALIGN16(rgb); NERF_CHECK_ALIGN16(dist); NERF_CHECK_ALIGN16(alpha); NERF_CHECK_ALIGN16(z);
     ChainFwdArgs a{};
     const int64_t n = (int64_t)n_rays * n_samples;
     a.n_pad = (int)((n + CROWS - 1) / CROWS * CROWS);

@@ -8,7 +8,8 @@ literal counterpart and use the nearest check of the entry:
   * nerf_render_eval_fused takes no n_pad (it derives it from n_rays x n_samples): its row-count
     cases are the sample count that does not tile the block and the sample total past 2^30;
   * nerf_chain_bwd has no bias: the backward entries' 16-byte case is the density head's weight
-    (wd), their other LDS-DMA source next to the weight images."""
+    (wd), their other LDS-DMA source next to the weight images.
+nerf_render_eval_fused also refuses an output (rgb, dist, alpha, z) that is not 16-byte aligned."""
 import re
 
 import pytest
@@ -184,6 +185,26 @@ def test_valid_arguments_are_what_the_cases_start_from(state, h16):
 @pytest.mark.parametrize("entry,edit,fragment", FORWARD_CASES, ids=_ids(FORWARD_CASES))
 def test_forward_entry_refuses(state, h16, entry, edit, fragment):
     _refused(entry, fragment, lambda: _forward(entry, state, edit))
+
+
+@pytest.mark.parametrize("which", ["rgb", "dist", "alpha", "z"])
+def test_eval_entry_refuses_a_misaligned_output(state, h16, dev, which):
+    """The header's pointer contract (16-byte aligned; alpha is stored as float4 for S >= 64): an
+    output 4 bytes off is refused on the host, nothing launches, the guarded outputs stay untouched."""
+    k = state
+    shapes = dict(rgb=(R0, 3), dist=(R0,), alpha=(R0, S0), z=(NP,))
+    G = {n: H.Guarded(s, dev) for n, s in shapes.items()}
+    outs = {n: g.t for n, g in G.items()}
+    g = G[which]
+    outs[which] = g.buf[H.GUARD + 1:H.GUARD + 1 + g.t.numel()]
+    assert outs[which].data_ptr() % 16 == 4
+    descs = H.chain_descs(k["runner"], [None] * 10, [None] * 10, [None] * 10)
+    _refused(EVAL, f"pointer '{which}' not 16-byte aligned",
+             lambda: _hip.render_eval_fused(k["o"], k["d"], k["view"], R0, S0, 0.01, 10.0, 0, descs, *k["heads"],
+                                            outs["rgb"], outs["dist"], outs["alpha"], outs["z"]))
+    torch.cuda.synchronize()
+    for n, gd in G.items():
+        assert gd.untouched(), n
 
 
 @pytest.mark.parametrize("entry,edit,fragment", BACKWARD_CASES, ids=_ids(BACKWARD_CASES))
