@@ -88,8 +88,11 @@ int nerf_encode_samples(const float* pts_o, const float* pts_d, const float* vie
  * pair form written by nerf_pack_weights in that mode.
  * x1_rmax / x2_rmax ([m], precision mode 2, required there): max |x| over each row of the
  * segment (as written by the producer of x: nerf_encode_samples, this function, ...).
- * y_rmax (optional, mode 2 only): receives max |y| per row; with n > 256 (several column
- * blocks) it is max-accumulated and must be zeroed by the caller.
+ * y_rmax (optional, mode 2 only): receives max |y| per row, whatever it held before: where the
+ * tile policy splits n over several column blocks the call zeroes it on the stream first and
+ * the blocks max-accumulate, so the caller owes no pre-zeroing at any n or policy.
+ * Alignment: x1, x2, w, w_split, y, bias (and v of nerf_linear_bwd_data) 16-byte aligned; ldx1,
+ * ldx2 and ldy multiples of 4, ldy >= n (NERF_EINVAL otherwise).
  * y_cmax (optional, mode 2 only): receives max |y| per column and 128-row group,
  * [m/128][n] (the column scales of nerf_linear_bwd_weight in mode 2).
  */

@@ -439,6 +439,10 @@ static int check_nt(const NTArgs& a, const char* fn) {
                "%s: leading dimension smaller than K", fn);
     NERF_CHECK((((uintptr_t)a.a1 | (uintptr_t)a.b | (uintptr_t)(a.a2 ? a.a2 : a.a1)) & 15u) == 0,
                "%s: operands must be 16-byte aligned", fn);
+    // the epilogues store the output and (bf16x3 kernels) read bias / v by float4
+    NERF_CHECK((((uintptr_t)a.c) & 15u) == 0 && a.ldc % 4 == 0,
+               "%s: the output must be 16-byte aligned with a row stride that is a multiple of 4", fn);
+    NERF_CHECK((((uintptr_t)a.bias | (uintptr_t)a.v) & 15u) == 0, "%s: bias / v must be 16-byte aligned", fn);
     NERF_CHECK(a.bs == nullptr || ((((uintptr_t)a.bs) & 15u) == 0 && a.bs_rows >= a.n),
                "%s: split weight image must be 16-byte aligned with at least n rows", fn);
     return NERF_OK;

@@ -508,7 +508,7 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void k_gemm_nt_x6(NTArgs p) {
                 for (int e = threadIdx.x; e < BM * MW; e += NT)
                     p.mask_out[(size_t)(m0 + e / MW) * p.ldmo + (n0 >> 5) + e % MW] = lmask[e];
             if (H && p.c_rmax) {
-                // one column block: plain stores; several: max-accumulate (caller zeroes c_rmax)
+                // one column block: plain stores; several: max-accumulate (launch_nt_x6 zeroed c_rmax)
                 for (int e = threadIdx.x; e < BM; e += NT) {
                     if (gridDim.y == 1) p.c_rmax[m0 + e] = __uint_as_float(lrm[e]);
                     else atomicMax(reinterpret_cast<uint32_t*>(p.c_rmax) + m0 + e, lrm[e]);
@@ -949,6 +949,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_gemm_tn_x6_seg(TNArgs pm, T
 template <int BM, int BN, int WM, int WN, int EPI>
 static void launch_nt_x6(const NTArgs& a, hipStream_t s, bool h16) {
     constexpr bool co = BM == 128 && BN == 256;   // fits two co-resident blocks per CU (fp16 pair)
+    // c_rmax: one column block stores the row max plainly, several max-accumulate it -- from zero,
+    // cleared here on the stream whatever tile the policy picked, so the caller owes nothing
+    if (h16 && a.c_rmax && a.n / BN > 1) (void)hipMemsetAsync(a.c_rmax, 0, (size_t)a.m * sizeof(float), s);
     if constexpr (EPI == EPI_FWD) {
         if (h16 && a.n_heads > 0) {   // fused output heads: their own instantiation (registers)
             hipLaunchKernelGGL((k_gemm_nt_x6<BM, BN, WM, WN, EPI, true, true, co ? 2 : 1, true>),

@@ -371,11 +371,11 @@ class FieldRunner:
 
     def _rmax_alloc(self, Np: int, dev):
         """Row-max buffer factory for precision mode 2 (None otherwise): a buffer for an
-        operand of `width` columns; wider than one 256-column GEMM block it is max-accumulated
-        by the kernel and starts at zero."""
+        operand of `width` columns.  Uninitialised: the GEMMs zero it themselves where several
+        column blocks max-accumulate (include/nerf_hip.h, y_rmax), at every tile policy."""
         if not self.h16:
             return lambda width: None
-        return lambda width: (torch.zeros if width > 256 else torch.empty)(Np, device=dev, dtype=torch.float32)
+        return lambda width: torch.empty(Np, device=dev, dtype=torch.float32)
 
     def _cmax_alloc(self, Np: int, dev, keep: bool = True):
         """Column-max buffer factory (mode 2, training only): [Np/128][width] per 128-row
